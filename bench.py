@@ -6,6 +6,7 @@ count, MIN_FREQ/MIN_BC solid filter, spectrum, adjacency clean-up) over one synt
 read set that is already resident in HBM when the timed region starts.
 
   python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs bench_outputs    (+ the last step's outputs, dump_outputs())
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -198,6 +199,77 @@ def leg_summary(secs, st):
             "n_solid": st["n_solid"], "n_items": st["n_items"], "n_overflow_items": st["n_overflow_items"],
             "ms_count": round(st["ms_count"], 2), "ms_part_count": round(st["ms_part_count"], 2),
             "ms_fallback": round(st["ms_fallback"], 2)}
+
+
+DUMP_BYTES_MAX = 64 << 20      # --dump-outputs: everything written, at most
+DUMP_SOLID_ROWS = 1 << 19      # dictionary entries kept (5 float64 columns: 20 MiB)
+DUMP_GOOD_LENS = 1 << 20       # trimmed lengths kept (index and value, float64: 16 MiB)
+
+
+def u64_halves(x):
+    """uint64 -> (low 32 bits, high 32 bits) as float64 columns: exact, where float64 of the whole word is not."""
+    x = np.asarray(x, np.uint64)
+    return (x & np.uint64(0xFFFFFFFF)).astype(np.float64), (x >> np.uint64(32)).astype(np.float64)
+
+
+def solid_sample(entries, m, workers=16):
+    """At most m dictionary entries chosen by their k-mer alone, whatever order the device holds them in: those with the
+    smallest values of a fixed multiplicative hash of (w0, w1), then sorted by (w0, w1).  The same dictionary gives the same
+    rows; a build that computes another dictionary shows it in the rows it keeps or in their values."""
+    from concurrent.futures import ThreadPoolExecutor
+    n = len(entries)
+    C1, C2 = np.uint64(0x9E3779B97F4A7C15), np.uint64(0xBF58476D1CE4E5B9)
+    thr = np.uint64(min(2 ** 64 - 1, int(2 ** 64 * 1.25 * m / max(1, n))))     # ~1.25 m candidates, then the m smallest
+
+    def pick(a):
+        w = entries[a:a + (1 << 22)]
+        h = w["w1"] * C2; h += w["w0"]; h *= C1                                   # (uint64 arithmetic wraps)
+        sel = h <= thr
+        return w[sel], h[sel]
+    with ThreadPoolExecutor(workers) as ex:                                           # (numpy lets go of the GIL in the loops)
+        got = list(ex.map(pick, range(0, n, 1 << 22)))
+    kept = np.concatenate([g[0] for g in got]) if got else entries[:0]
+    h = np.concatenate([g[1] for g in got]) if got else np.zeros(0, np.uint64)
+    if len(kept) > m:
+        kept = kept[np.lexsort((kept["w1"], kept["w0"], h))[:m]]                   # (ties of h settled by the k-mer)
+    kept = kept[np.lexsort((kept["w1"], kept["w0"]))]
+    w0l, w0h = u64_halves(kept["w0"])
+    w1l, w1h = u64_halves(kept["w1"])
+    return np.stack([w0l, w0h, w1l, w1h, kept["count_ctx"].astype(np.float64)], axis=1)
+
+
+def dump_outputs(d, out_dir):
+    """--dump-outputs: what the last timed step computed, as a caller of dfk_count_device receives it (rank 0's share in a
+    multi-rank run), written as out_dir/<name>.npy in float64 so that two builds can be compared output for output:
+      counts         n_reads, n_inst, n_distinct, n_solid
+      spectrum       the k-mer spectrum, whole: rows (count, solid k-mers with that count) for every count that occurs
+                     (k such rows need k(k+1)/2 instances: 4.2e5 rows at most for 8.8e10)
+      solid_digest   dfk_solid_digest of the whole dictionary: sum low, sum high, xor low, xor high (32-bit halves)
+      solid_sample   rows w0 low, w0 high, w1 low, w1 high, count_ctx of a fixed sample of the entries (solid_sample())
+      good_lens      rows (read index, trimmed length) at a seeded draw of read indices, the same for every build
+    Fields the library leaves unspecified at this point (edge_id, bc, pad) are not written."""
+    os.makedirs(out_dir, exist_ok=True)
+    st = d.stats()
+    hist = d.spectrum()
+    nz = np.flatnonzero(hist)
+    arrays = {"counts": np.array([st[k] for k in ("n_reads", "n_inst", "n_distinct", "n_solid")], np.float64),
+              "spectrum": np.stack([nz.astype(np.float64), hist[nz].astype(np.float64)], axis=1)}
+    lo, hi = u64_halves(d.digest())
+    arrays["solid_digest"] = np.array([lo[0], hi[0], lo[1], hi[1]])
+    entries = d.solid_unsorted()
+    arrays["solid_sample"] = solid_sample(entries, DUMP_SOLID_ROWS)
+    del entries
+    n = st["n_reads"]
+    gl = d.good_lens()
+    idx = np.arange(n) if n <= DUMP_GOOD_LENS else np.sort(np.random.default_rng(SEED).choice(n, DUMP_GOOD_LENS, replace=False))
+    arrays["good_lens"] = np.stack([idx.astype(np.float64), gl[idx].astype(np.float64)], axis=1)
+    del gl
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES_MAX, f"--dump-outputs would write {total} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] outputs of the last timed step: {', '.join(f'{k}{list(a.shape)}' for k, a in arrays.items())} -> {out_dir}",
+          file=sys.stderr)
 
 
 def write_read_files(rs, head, workers=8):
@@ -515,7 +587,12 @@ def main():
     ap.add_argument("--one-device", action="store_true", help="every rank uses cuda:0 (rehearsal on a one-GPU box)")
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="rehearsal on one GPU: run rank 0 of this many ranks against replicas of itself (not a benchmark result)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64, at most 64 MB; "
+                         "the dictionary and the trimmed lengths as fixed samples): see dump_outputs()")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: the result is the timed steps' rate")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -616,6 +693,8 @@ def main():
                            "n_passes": tm["n_passes"]}
         else:
             dist_timing = {"rank0": {k: round(float(v), 3) for k, v in tm.items()}}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(d, args.dump_outputs)
     d.close()                                        # the legs below make their own contexts
     if rank == 0:
         ms_step = 1e3 * elapsed / args.steps

@@ -33,6 +33,7 @@
 #include <ctime>
 #include <fcntl.h>
 #include <functional>
+#include <future>
 #include <exception>
 #include <cerrno>
 #include <map>
@@ -629,7 +630,10 @@ int main(int argc, char** argv)
         auto in_background = [&](std::function<void()> fn) {
             background.emplace_back([&, fn] { try { fn(); } catch (...) { if (!bg_failed.exchange(true)) bg_err = std::current_exception(); } });
         };
+        std::vector<std::shared_future<void>> table_checks;   // .qualp's offset tables, checked beside what follows
+        auto tables_checked = [&] { for (auto& f : table_checks) f.get(); };    // (a refused table throws here)
         auto join_background = [&] {
+            tables_checked();
             for (auto& x : background) x.join();
             background.clear();
             if (bg_failed) std::rethrow_exception(bg_err);
@@ -653,7 +657,7 @@ int main(int argc, char** argv)
             struct DenseSize { const uint8_t* lens; uint64_t operator()(uint64_t r) const { return ((uint64_t)ld32(lens + 4 * r) + 3) / 4; } };
             x.fb.check_offsets(DenseSize{lens}, ".fastb: read length disagrees with its byte count");
             FeudalMap* qp = &x.qp;
-            in_background([qp] { qp->check_offsets(); });
+            table_checks.push_back(std::async(std::launch::async, [qp] { qp->check_offsets(); }).share());
         }
         if (select_frac.size() == 1 && heads.size() > 1) select_frac.assign(heads.size(), select_frac[0]);
         if (select_frac.size() != heads.size()) throw std::runtime_error("LR_SELECT_FRAC needs one value per LR input");   // DfTools.cc:96
@@ -747,7 +751,8 @@ int main(int argc, char** argv)
         };
         // fast path: the reference's random stream is advanced by one draw per pair in LoadData (all kept), then
         // WriteSubSample draws once more per pair -- 2 x 10^9 sequential draws at human scale, off the critical path
-        if (fast) in_background([&, subsample] { for (uint64_t i = 0; i < n_reads / 2; ++i) (void)rng.next(); subsample(); });
+        // (the sample is read through .qualp's table: checked first)
+        if (fast) in_background([&, subsample, checks = table_checks] { for (uint64_t i = 0; i < n_reads / 2; ++i) (void)rng.next(); for (auto& f : checks) f.get(); subsample(); });
         else subsample();
         printf("%s: loaded %llu reads\n", date().c_str(), (unsigned long long)n_reads);
         for (const DataSet& d : datasets) printf("\t%s starts at %ld\n", d.dt == 2 ? "UNBAR_10X" : "BAR_10X", (long)d.start);
@@ -851,6 +856,7 @@ int main(int argc, char** argv)
         printf("%s: computing quality histogram\n", date().c_str());
         std::vector<int64_t> qh((size_t)2 * max_len * 256, 0);                  // [parity][pos][q]
         if (!device_hist) {
+            tables_checked();                                                   // (read through .qualp's table on the host: checked first)
             std::vector<std::unique_ptr<QualHist>> part(g_threads + 1);
             parallel_ranges(n_reads, [&](unsigned t, uint64_t lo, uint64_t hi) {
                 part[t].reset(new QualHist(max_len));

@@ -1,8 +1,23 @@
 """Seeded synthetic stLFR fastq.gz pairs for the ParseBarcodedFastqs tests (names "@id#b1_b2_b3/1<TAB>...", barcode
 0_0_0 = unbarcoded; split_barcode_PEXXX_42_unsort_reads.pl's format).  Harness only."""
 import gzip
+import hashlib
 
 import numpy as np
+
+
+def case_name(n_pairs, seed, n_bc, ragged, extra):
+    """The key of make_fastq(n_pairs, seed, n_bc, ragged) run with the arguments `extra` in tests/golden/pbf_ref.json."""
+    return f"p{n_pairs}_s{seed}_bc{n_bc}" + ("_ragged" if ragged else "") + "".join("_" + e for e in extra)
+
+
+def fastq_digest(path1, path2):
+    """SHA-256 of the two files' text (not of the .gz bytes: gzip stamps the time)."""
+    h = hashlib.sha256()
+    for p in (path1, path2):
+        with gzip.open(p, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()
 
 
 def make_fastq(path1, path2, n_pairs, seed, n_bc=40, L=100, ragged=False):

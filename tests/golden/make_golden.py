@@ -8,6 +8,7 @@ BinaryWriter/KmerDict::recomputeAdjacencies compiled in place from /root/referen
 restated; see oracle/ref_driver.cc).  Only data is committed: no reference source or script.
 
   python tests/golden/make_golden.py        (needs oracle/_ref/refdrv: oracle/build_ref.sh)
+  python tests/golden/make_golden.py pbf_ref    (tests/golden/pbf_ref.json alone)
 """
 import os
 import struct
@@ -405,7 +406,40 @@ def main():
     np.savez_compressed(os.path.join(HERE, "expect_frag_k48.npz"), solid_post=post)
     assert ne >= 870
     print("graph frag: solid", len(post), "HBV edges", ne)
+    pbf_ref()
+
+
+# The seeded inputs the ParseBarcodedFastqs tests compare with the reference's binary (tests/test_parse_barcoded_fastqs.py,
+# tests/test_gpu_pbf.py): (pairs, seed, barcodes, ragged, arguments)
+PBF_REF_CASES = [(2000, 11, 40, True, ("NUM_BUCKETS=5",)), (1500, 12, 300, False, ()), (800, 13, 3, True, ("NUM_BUCKETS=256",)),
+                 (1200, 14, 25, True, ("NUM_BUCKETS=2",)), (1500, 15, 30, False, ("NUM_BUCKETS=7", "READS_PER_BC=90"))] + \
+                [(3000, 41, 40, True, extra) for extra in (("NUM_BUCKETS=8",), ("NUM_BUCKETS=16",), ("NUM_BUCKETS=9", "READS_PER_BC=400"),
+                                                           ("NUM_BUCKETS=64",))]
+
+
+def pbf_ref():
+    """tests/golden/pbf_ref.json: what the reference's own ParseBarcodedFastqs (single-threaded, see oracle/build_ref.sh)
+    writes for each of PBF_REF_CASES, as SHA-256 of the three files, with the SHA-256 of the input they were written from."""
+    import hashlib
+    import json
+    import tempfile
+    from tests.fastq_synth import case_name, fastq_digest, make_fastq
+    binary = os.path.join(ROOT, "oracle", "_ref", "ParseBarcodedFastqs")
+    if not os.path.exists(binary):
+        raise SystemExit("oracle/_ref/ParseBarcodedFastqs missing: run oracle/build_ref.sh in the build container")
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        for pairs, seed, n_bc, ragged, extra in PBF_REF_CASES:
+            make_fastq(d + "/a_1.fq.gz", d + "/a_2.fq.gz", pairs, seed, n_bc=n_bc, ragged=ragged)
+            subprocess.check_call([binary, "FASTQS={" + d + "/a_1.fq.gz," + d + "/a_2.fq.gz}", "OUT_HEAD=" + d + "/o/reads", "NUM_THREADS=1", *extra],
+                                  stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+            e = out[case_name(pairs, seed, n_bc, ragged, extra)] = {"input": fastq_digest(d + "/a_1.fq.gz", d + "/a_2.fq.gz")}
+            for ext in ("fastb", "qualp", "bci"):
+                e[ext] = hashlib.sha256(open(f"{d}/o/reads.{ext}", "rb").read()).hexdigest()
+            subprocess.check_call(["rm", "-rf", d + "/o"])
+    json.dump(out, open(os.path.join(HERE, "pbf_ref.json"), "w"), indent=1)
+    print("pbf_ref:", len(out), "cases")
 
 
 if __name__ == "__main__":
-    main()
+    pbf_ref() if sys.argv[1:] == ["pbf_ref"] else main()

@@ -1,15 +1,15 @@
 """SURVEY 8(f)-3 on the GPU: ParseBarcodedFastqs with the pair order, the 2-bit packing and the PQVec encoder on the device
 (dfk_pbf_run, the program's default path) -- byte for byte against the fixture the reference's own binary wrote
-(tests/golden/pbf/), against that binary where it is present (oracle/_ref/ParseBarcodedFastqs travels with the repository),
-and against the program's HOST=True path on seeded inputs: ragged lengths, duplicates (ties in the per-barcode order), reads
-with N, READS_PER_BC, bucket counts from 1 to 256, and a set larger than MAX_MEM_GB done in groups of buckets."""
+(tests/golden/pbf/), against what that binary wrote from the same seeded inputs (tests/golden/pbf_ref.json), and against
+the program's HOST=True path on seeded inputs: ragged lengths, duplicates (ties in the per-barcode order), reads with N,
+READS_PER_BC, bucket counts from 1 to 256, and a set larger than MAX_MEM_GB done in groups of buckets."""
 import gzip
 import os
 
 import pytest
 
-from tests.fastq_synth import make_fastq
-from tests.test_parse_barcoded_fastqs import OURS, REF, run, same_files
+from tests.fastq_synth import case_name, make_fastq
+from tests.test_parse_barcoded_fastqs import OURS, run, same_as_reference, same_files
 
 pytestmark = pytest.mark.gpu
 
@@ -33,10 +33,8 @@ def test_device_path_matches_host_path_and_reference_binary(tmp_path, pairs, see
     h = run(OURS, fq1, fq2, f"{tmp_path}/host/reads", "NUM_THREADS=4", *extra)
     assert h.returncode == 0, h.stderr
     same_files(f"{tmp_path}/dev/reads", f"{tmp_path}/host/reads")
-    if os.path.exists(REF) and "NUM_BUCKETS=1" not in extra:                 # (the reference aborts on one bucket)
-        r = run(REF, fq1, fq2, f"{tmp_path}/ref/reads", "NUM_THREADS=1", *extra)
-        assert r.returncode == 0, r.stdout + r.stderr
-        same_files(f"{tmp_path}/dev/reads", f"{tmp_path}/ref/reads")
+    if "NUM_BUCKETS=1" not in extra:                                          # (the reference aborts on one bucket)
+        same_as_reference(f"{tmp_path}/dev/reads", fq1, fq2, case_name(pairs, seed, n_bc, ragged, extra))
 
 
 def test_two_hundred_thousand_pairs_and_groups_of_buckets(tmp_path):

@@ -1,8 +1,11 @@
 """ParseBarcodedFastqs: stLFR fastq.gz pairs -> barcode-sorted .fastb/.qualp/.bci, byte for byte against
 the reference's own binary -- oracle/_ref/ParseBarcodedFastqs, built from 10X/ParseBarcodedFastqs.cc where it lies
-(flags only) -- when it is there (the build container), and against the fixture it wrote (tests/golden/pbf/) anywhere.
+(flags only): against the fixture it wrote (tests/golden/pbf/) and, on seeded inputs, against the SHA-256 of the files it
+wrote from them (tests/golden/pbf_ref.json; both made by tests/golden/make_golden.py).
 These run the program's HOST=True path (its own host code for the pair order, the packing and the PQVec encoder), on the
 CPU; the default path -- the same three steps on the MI355X (dfk_pbf_run) -- is compared with both in tests/test_gpu_pbf.py."""
+import hashlib
+import json
 import os
 import subprocess
 
@@ -10,11 +13,11 @@ import numpy as np
 import pytest
 
 from superplus_amd import feudal
-from tests.fastq_synth import make_fastq
+from tests.fastq_synth import case_name, fastq_digest, make_fastq
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OURS = os.path.join(ROOT, "superplus_amd", "ParseBarcodedFastqs")
-REF = os.path.join(ROOT, "oracle", "_ref", "ParseBarcodedFastqs")
+REF_WRITTEN = os.path.join(ROOT, "tests", "golden", "pbf_ref.json")
 
 
 def run(binary, fq1, fq2, head, *extra, device=False):
@@ -25,6 +28,15 @@ def run(binary, fq1, fq2, head, *extra, device=False):
 def same_files(a, b):
     for ext in ("fastb", "qualp", "bci"):
         assert open(f"{a}.{ext}", "rb").read() == open(f"{b}.{ext}", "rb").read(), ext
+
+
+def same_as_reference(head, fq1, fq2, key):
+    """head.{fastb,qualp,bci} against what the reference's binary wrote from the same input with the same arguments
+    (single-threaded): the SHA-256 of each file in tests/golden/pbf_ref.json."""
+    exp = json.load(open(REF_WRITTEN))[key]
+    assert fastq_digest(fq1, fq2) == exp["input"], "make_fastq no longer makes the input the reference's files were written from"
+    for ext in ("fastb", "qualp", "bci"):
+        assert hashlib.sha256(open(f"{head}.{ext}", "rb").read()).hexdigest() == exp[ext], ext
 
 
 def test_fixture_written_by_the_reference_binary(tmp_path, golden_dir):
@@ -38,18 +50,15 @@ def test_fixture_written_by_the_reference_binary(tmp_path, golden_dir):
     assert bci[0] == 0 and bci[-1] == len(rlen) == 600 and np.all(np.diff(bci) >= 0) and np.all(bci % 2 == 0)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference binary exists in the build container only")
 @pytest.mark.parametrize("pairs,seed,n_bc,ragged,extra", [
     (2000, 11, 40, True, ("NUM_BUCKETS=5",)), (1500, 12, 300, False, ()), (800, 13, 3, True, ("NUM_BUCKETS=256",)),
     (1200, 14, 25, True, ("NUM_BUCKETS=2",)), (1500, 15, 30, False, ("NUM_BUCKETS=7", "READS_PER_BC=90"))])
 def test_against_the_reference_binary(tmp_path, pairs, seed, n_bc, ragged, extra):
     fq1, fq2 = f"{tmp_path}/a_1.fq.gz", f"{tmp_path}/a_2.fq.gz"
     make_fastq(fq1, fq2, pairs, seed, n_bc=n_bc, ragged=ragged)
-    r = run(REF, fq1, fq2, f"{tmp_path}/ref/reads", "NUM_THREADS=1", *extra)
-    assert r.returncode == 0, r.stdout + r.stderr
     o = run(OURS, fq1, fq2, f"{tmp_path}/ours/reads", "NUM_THREADS=4", *extra)
     assert o.returncode == 0, o.stderr
-    same_files(f"{tmp_path}/ours/reads", f"{tmp_path}/ref/reads")
+    same_as_reference(f"{tmp_path}/ours/reads", fq1, fq2, case_name(pairs, seed, n_bc, ragged, extra))
 
 
 def test_one_bucket_works(tmp_path):
@@ -99,10 +108,7 @@ def test_a_set_larger_than_max_mem_gb_is_done_in_groups_of_buckets(tmp_path, mem
     n_passes = int(o.stderr.split("allowed: ")[1].split()[0])
     assert n_passes >= 3, o.stderr
     same_files(f"{tmp_path}/groups/reads", f"{tmp_path}/whole/reads")
-    if os.path.exists(REF):
-        r = run(REF, fq1, fq2, f"{tmp_path}/ref/reads", "NUM_THREADS=1", *extra)
-        assert r.returncode == 0, r.stdout + r.stderr
-        same_files(f"{tmp_path}/groups/reads", f"{tmp_path}/ref/reads")
+    same_as_reference(f"{tmp_path}/groups/reads", fq1, fq2, case_name(3000, 41, 40, True, extra))
 
 
 def test_refuses_an_input_that_does_not_fit_max_mem_gb(tmp_path):
