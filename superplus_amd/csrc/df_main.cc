@@ -760,7 +760,6 @@ int main(int argc, char** argv)
         // ---- barcode expansion (DF.cc:447-452) and createDict on the GPU.  With the inputs mapped in place (fast path) the upload
         //      and the count start NOW, in a thread of their own, while this one computes the side files below; otherwise
         //      they run where the reference has them.
-        std::unique_ptr<int32_t[]> bc;                                          // (not a vector: 7 GB need not be zeroed by one thread first)
         dfk_config cfg{};
         cfg.abi_version = DFK_ABI_VERSION; cfg.K = K; cfg.min_qual = (uint32_t)atoi(a["MIN_QUAL"].c_str());
         cfg.min_freq = (uint32_t)atoi(a["MIN_FREQ"].c_str()); cfg.min_bc = (uint32_t)atoi(a["MIN_BC"].c_str());
@@ -799,32 +798,22 @@ int main(int argc, char** argv)
         int count_rc = 0; bool create_failed = false; std::string count_err; double t_count = 0;
         // frag_reads_orig.qhist: counted on the device from the reads the count keeps there (the pathing wants them), behind the
         // count, once this thread has been through the read lengths; counted here when the device keeps nothing
-        const bool device_hist = fast && !sharded && !truthy(a["EXIT_LOAD"]) && want_paths && !getenv("DF_HOST_QHIST");
+        const bool device_hist = fast && !sharded && !truthy(a["EXIT_LOAD"]) && want_paths;
         std::atomic<int> max_len_known{-1};
         std::vector<int64_t> qh_dev; std::string qh_err; double t_qhist = 0;
         // The barcode expansion of DF.cc:447-452 (7 GB of int32 at configs[1]) and the .fastb offset table (14 GB: a running sum of
         // the read lengths, as the validation above has just established) are made on the device from the 80 MB index and the
-        // lengths (dfk_count_bci, base_off = NULL): neither is written by the host or crosses PCIe.  DF_HOST_BC=1: as before.
-        const bool host_bc = getenv("DF_HOST_BC") != nullptr;
+        // lengths (dfk_count_bci, base_off = NULL): neither is written by the host or crosses PCIe.
         auto count_job = [&] {
-            const double tj0 = now_s();
-            if (host_bc) {
-                bc.reset(new int32_t[std::max<uint64_t>(1, n_reads)]);
-                parallel_ranges(n_reads, [&](unsigned, uint64_t lo, uint64_t hi) { memset(bc.get() + lo, 0, 4 * (hi - lo)); });      // (reads no barcode's range holds: 0)
-                parallel_ranges(bci.size() - 1, [&](unsigned, uint64_t lo, uint64_t hi) {
-                    for (uint64_t b = lo; b < hi; ++b) for (int64_t r = bci[b]; r < bci[b + 1]; ++r) bc[r] = (int32_t)b;
-                }, 1024);
-            }
-            const double tj1 = now_s();
+            const double tj = now_s();
             if (dfk_create(&cfg, &ctx)) { create_failed = true; count_err = dfk_last_error(); return; }
-            if (getenv("DFK_TRACE")) fprintf(stderr, "[DF] barcodes expanded in %.3f s, dfk_create %.3f s, %.3f s after the process started\n", tj1 - tj0, now_s() - tj1, now_s() - t_start);
+            if (getenv("DFK_TRACE")) fprintf(stderr, "[DF] dfk_create %.3f s, %.3f s after the process started\n", now_s() - tj, now_s() - t_start);
             if (fast)                                                           // the arrays are maps of these files: what has been uploaded leaves the page table (see below)
                 for (const Mapped* m : {&ins[0].fb.m, &ins[0].qp.m})
                     if (m->p && dfk_hint_file_range(ctx, m->p, m->n, -1, 0)) { create_failed = true; count_err = dfk_last_error(); return; }
             printf("%s: building dictionary on the GPU\n", date().c_str());
             const double tc = now_s();
-            if (host_bc) count_rc = dfk_count(ctx, h_packed, (const uint64_t*)h_boff, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, bc.get(), n_reads);
-            else if (fast) count_rc = dfk_count_bci(ctx, h_packed + (n_reads ? ld64(h_boff) : 0), nullptr, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, bci.data(), bci.size(), n_reads);   // (dense: validated above)
+            if (fast) count_rc = dfk_count_bci(ctx, h_packed + (n_reads ? ld64(h_boff) : 0), nullptr, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, bci.data(), bci.size(), n_reads);   // (dense: validated above)
             else count_rc = dfk_count_bci(ctx, h_packed, (const uint64_t*)h_boff, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, bci.data(), bci.size(), n_reads);
             if (count_rc) count_err = dfk_last_error();
             t_count = now_s() - tc;
@@ -914,7 +903,6 @@ int main(int argc, char** argv)
         if (rc) { fprintf(stderr, "DF: %s\n", count_err.c_str()); join_background(); return rc == DFK_E_NOMEM ? 185 : 1; }        // Martian::exit code
         dfk_stats st{}; dfk_get_stats(ctx, &st);
         T.upload = 1e-3 * st.ms_upload; T.count = t_count - T.upload;
-        bc.reset();
         if (fast) {
             // The mapped inputs are on the device (and stay there for the pathing), and the transfer lanes have dropped what they
             // copied from the page table (the hint above): unmapping them is cheap now, where it would have been three seconds
@@ -974,16 +962,9 @@ int main(int argc, char** argv)
                 const double ti = now_s();
                 printf("%s: inverting paths index\n", date().c_str());
                 if (reserve_inv_thread.joinable()) reserve_inv_thread.join();
-                if (getenv("DF_INDEX_THEN_DUPS")) {                             // (one after the other, each on its own clock)
-                    if (dfk_paths_index_write(ctx, dir.c_str())) throw std::runtime_error(dfk_last_error());
-                    t_index = now_s() - ti;
-                    const double td = now_s();
-                    if (dfk_dups_write(ctx, (dir + "/a.dup").c_str(), &n_dup)) throw std::runtime_error(dfk_last_error());
-                    t_dups = now_s() - td;
-                } else {                                                        // a.paths.inv's lists go to the file while the duplicates are marked
-                    if (dfk_paths_index_dups_write(ctx, dir.c_str(), (dir + "/a.dup").c_str(), &n_dup)) throw std::runtime_error(dfk_last_error());
-                    t_index = now_s() - ti;                                     // (both: mark_dups_s stays 0)
-                }
+                // a.paths.inv's lists go to the file while the duplicates are marked
+                if (dfk_paths_index_dups_write(ctx, dir.c_str(), (dir + "/a.dup").c_str(), &n_dup)) throw std::runtime_error(dfk_last_error());
+                t_index = now_s() - ti;                                         // (index and marks together: mark_dups_s stays 0)
                 mark("index and duplicate marks done");
                 paths_writer.join();
                 mark("a.paths written");

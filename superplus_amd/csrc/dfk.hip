@@ -435,12 +435,8 @@ struct ScanJob {
     ~ScanJob() { for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } }
 };
 
-// (the register scan takes ranges; the general scan -- other minimizer lengths, DFK_OLD_SCAN -- only everything at once)
-template <int K> bool scan_takes_ranges(const dfk_ctx* c)
-{
-    static const bool old_scan = getenv("DFK_OLD_SCAN") != nullptr;
-    return c->cfg.minimizer_len == 16 && !old_scan;
-}
+// (the register scan takes ranges; the general scan -- other minimizer lengths -- only everything at once)
+template <int K> bool scan_takes_ranges(const dfk_ctx* c) { return c->cfg.minimizer_len == 16; }
 
 template <int K>
 int scan_begin(dfk_ctx* c, const Inputs& in, uint32_t log2_world, int64_t read_id0, BucketTable* T, bool by_class, ScanJob* J)
@@ -452,7 +448,7 @@ int scan_begin(dfk_ctx* c, const Inputs& in, uint32_t log2_world, int64_t read_i
     if (by_class) { rc = c->alloc(T->class_hist, J->n_bins * 8, "class counters", true); if (rc) return rc; HIP_TRY(hipMemsetAsync(T->class_hist.p, 0, J->n_bins * 8, c->stream)); }
     else { rc = c->alloc(T->acc, J->nb * 8, "bucket counters", true); if (rc) return rc; }
     rc = c->alloc(T->summ, std::max<uint64_t>(1, in.n_reads) * 16, "run summaries", true); if (rc) return rc;
-    rc = c->alloc(T->classes, read_classes_bytes(std::max<uint64_t>(1, in.n_reads)), "read bucket classes", true); if (rc) return rc;
+    rc = c->alloc(T->classes, std::max<uint64_t>(1, in.n_reads) * 4, "read bucket classes", true); if (rc) return rc;
     if (!by_class) HIP_TRY(hipMemsetAsync(T->acc.p, 0, J->nb * 8, c->stream));
     // reads whose runs do not fit a summary are listed by the scan itself (two in 10^5 at 2x100 bp); if the list
     // outgrows the room set aside for it the summaries are searched instead
@@ -744,17 +740,6 @@ int count_run_end(dfk_ctx* c, CountRun* R)
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof z);
     }
 #endif
-#ifdef DFK_PROBE_STATS
-    {
-        unsigned long long ps[4] = {};
-        (void)hipMemcpyFromSymbol(ps, HIP_SYMBOL(g_probe_stats), sizeof ps);
-        fprintf(stderr, "[dfk] probe stats: %.2f loop iterations per batch, %.3f probes and %.3f lock waits per instance (%llu batches)\n",
-                (double)ps[0] / (double)std::max(1ull, ps[1]), (double)ps[2] / (64.0 * std::max(1ull, ps[1])),
-                (double)ps[3] / (64.0 * std::max(1ull, ps[1])), ps[1]);
-        unsigned long long z[4] = {};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_probe_stats), z, sizeof z);
-    }
-#endif
     DevBuf d_max; int rc = c->alloc(d_max, 16, "max bin"); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(d_max.p, 0, 16, c->stream));
     hipLaunchKernelGGL(k_hist_max, dim3(1024), dim3(256), 0, c->stream, (const unsigned long long*)R->d_hist.p, HIST_GLOBAL_BINS,
@@ -820,8 +805,7 @@ int launch_count(dfk_ctx* c, const Partition& P, const ItemRange* d_items, uint6
     if (c->after_count_launch || c->pending_blist >= 0) {
         // what the second stream is about to run beside this launch waits until its persistent workgroups are all in place
         // (at most 2 ms: then it goes ahead and the gate says so)
-        static const bool no_gate = getenv("DFK_NO_GATE") != nullptr;
-        if (!no_gate) hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, c->stream2, (const unsigned int*)c->d_resident, c->resident_target, 200000ull, c->d_resident + 1);
+        hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, c->stream2, (const unsigned int*)c->d_resident, c->resident_target, 200000ull, c->d_resident + 1);
     }
     if (c->after_count_launch) { std::function<int()> f; f.swap(c->after_count_launch); rc = f(); if (rc) return rc; }
     rc = launch_boundary_list(c); if (rc) return rc;
@@ -1995,26 +1979,19 @@ int write_parts_unsorted(dfk_ctx* c, int fd, bool pre, uint64_t first_byte = 16)
     }
     struct Pending { uint64_t bytes = 0, file_off = 0; bool live = false; };
     std::vector<Pending> pend(2 * (size_t)xfer_threads());
-    // The lanes store through a shared mapping of the file: concurrent pwrite()s to ONE file serialise on its inode
-    // lock (measured on tmpfs: 3.7 GB/s with 16 lanes, 50 GB in 13 s), page faults on a mapping do not.
     // Measured on the GPU box's tmpfs (tools/fs_write_scaling.cc, 16 GB into one file): ONE thread pwrite()s 8.6 GB/s,
     // 16 threads 6.6 GB/s (they serialise on the file's page-cache lock), a shared mapping 3.7-5.2 GB/s.  So the lanes
     // keep the device copies in flight in parallel and take turns at the file: one writer at a time.
-    char* map = nullptr;
-    if (getenv("DFK_KVEC_MMAP") && at > 16) { map = (char*)mmap(nullptr, at, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0); if (map == (char*)MAP_FAILED) map = nullptr; }
     std::mutex file_turn;
     auto flush = [&](XferLane& l, unsigned t, int k) -> int {      // the chunk sitting in buffer k goes to the file
         Pending& p = pend[2 * t + k];
         if (!p.live) return 0;
         HIP_TRY(hipEventSynchronize(l.ev[k]));
-        if (map) memcpy(map + p.file_off, l.pin[k], p.bytes);
-        else {
-            std::lock_guard<std::mutex> turn(file_turn);
-            for (uint64_t done = 0; done < p.bytes;) {
-                const ssize_t w = pwrite(fd, (const char*)l.pin[k] + done, p.bytes - done, (off_t)(p.file_off + done));
-                if (w <= 0) return fail(DFK_E_ARG, "short write to the k-mer file");
-                done += (uint64_t)w;
-            }
+        std::lock_guard<std::mutex> turn(file_turn);
+        for (uint64_t done = 0; done < p.bytes;) {
+            const ssize_t w = pwrite(fd, (const char*)l.pin[k] + done, p.bytes - done, (off_t)(p.file_off + done));
+            if (w <= 0) return fail(DFK_E_ARG, "short write to the k-mer file");
+            done += (uint64_t)w;
         }
         p.live = false;
         return 0;
@@ -2030,7 +2007,6 @@ int write_parts_unsorted(dfk_ctx* c, int fd, bool pre, uint64_t first_byte = 16)
             return flush(l, t, k ^ 1);                              // the other buffer's chunk is written while this one is in flight
         },
         [&](unsigned t, XferLane& l) -> int { int r = flush(l, t, 0); return r ? r : flush(l, t, 1); });
-    if (map && munmap(map, at) != 0 && !rc) return fail(DFK_E_ARG, "cannot unmap the k-mer file");
     return rc;
 }
 
@@ -2089,7 +2065,7 @@ int dfk_create(const dfk_config* cfg, dfk_ctx** out)
         int lo_pri = 0, hi_pri = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri);      // numerically lowest = highest priority
         HIP_TRY(hipStreamCreateWithPriority(&c->stream, hipStreamDefault, hi_pri));
-        HIP_TRY(hipStreamCreateWithPriority(&c->stream2, hipStreamDefault, getenv("DFK_S2_SAME_PRIO") ? hi_pri : lo_pri));
+        HIP_TRY(hipStreamCreateWithPriority(&c->stream2, hipStreamDefault, lo_pri));
     }
     HIP_TRY(hipMalloc((void**)&c->d_resident, 64));
     HIP_TRY(hipMemset(c->d_resident, 0, 64));

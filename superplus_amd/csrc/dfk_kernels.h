@@ -125,20 +125,6 @@ struct PartParams {
 // not look at the other reads at all: a read has ~4 runs, so a pass over 1/8 of the buckets needs ~45 % of the
 // reads, one over 1/32 of them 11 %.
 constexpr uint32_t SWEEP_CLASSES = 32;
-// -DDFK_RUN_CLASSES (measured, not the default): behind the masks, in the same buffer, per read one 64-bit word with the
-// class of EACH of its (up to ten) runs, five bits a run.  A sweep then rebuilds the bucket -- a random read of the
-// minimizer's bases and a hash -- only for the runs whose class the pass touches instead of for every run of every listed
-// read (that look-up is four times as frequent as the records a sweep writes).  At configs[1]: a sweep takes 81.7 ms
-// instead of 95.9 -- but the 8 bytes per read (14.4 GB) make it 11 passes instead of 9, and the step comes out the same
-// (1504 against 1508 ms); the sweeps hide under the counts either way.
-#ifndef DFK_RUN_CLASSES
-__host__ __device__ inline uint64_t read_classes_bytes(uint64_t n_reads) { return n_reads * 4; }
-__device__ __forceinline__ const uint64_t* run_classes_of(const uint32_t*, uint64_t) { return nullptr; }
-#else
-__host__ __device__ inline uint64_t read_classes_bytes(uint64_t n_reads) { return ((n_reads + 1) & ~1ull) * 4 + n_reads * 8; }
-__device__ __forceinline__ const uint64_t* run_classes_of(const uint32_t* read_classes, uint64_t n_reads)
-{ return read_classes ? reinterpret_cast<const uint64_t*>(read_classes + ((n_reads + 1) & ~1ull)) : nullptr; }
-#endif
 __host__ __device__ inline uint32_t sweep_class_of(uint32_t local_bucket, uint32_t log2_local)
 { return log2_local > 5 ? local_bucket >> (log2_local - 5) : local_bucket; }
 __host__ __device__ inline uint32_t sweep_class_mask(uint32_t sub_lo, uint32_t sub_n, uint32_t log2_local)
@@ -247,12 +233,11 @@ partition_read(uint64_t r, uint32_t* smem, uint32_t* __restrict__ lh,
     const uint32_t M = pp.M, W = pp.W;
     const uint32_t gl = r < n_reads ? good_len[r] : 0;
     if (gl < (uint32_t)K + 1) {                                  // Kmerizer::map: len < K+1 emits nothing (:153)
-        if (!WRITE && r < n_reads) { summaries[r] = uint4{0, 0, 0, 0}; if (read_classes) { read_classes[r] = 0u; if (uint64_t* rc_ = const_cast<uint64_t*>(run_classes_of(read_classes, n_reads))) rc_[r] = 0ull; } }
+        if (!WRITE && r < n_reads) { summaries[r] = uint4{0, 0, 0, 0}; if (read_classes) read_classes[r] = 0u; }
         return;
     }
     uint32_t Pi = 0, cur_rel = 0;                                // !WRITE: where the prefix minimum sits; minimizer offset of the open run
     uint32_t cmask = 0;                                          // !WRITE: classes of the runs' buckets (the sweeps' prefilter)
-    uint64_t rcls = 0;                                           // !WRITE: ... and run by run, five bits each
     const uint32_t log2_local = pp.log2_nb - pp.log2_world;
 
     const uint64_t byte0 = base_off[r];
@@ -297,9 +282,7 @@ partition_read(uint64_t r, uint32_t* smem, uint32_t* __restrict__ lh,
         if (!WRITE) {
             if (lh) { const uint32_t bin = class_bin(cur_b, pp); atomicAdd(&lh[bin], 1u); atomicAdd(&lh[(PART_CLASSES << pp.log2_world) + bin], cur_nk); }
             else atomicAdd(&bucket_acc[cur_b], (1ull << 32) | cur_nk);
-            const uint32_t cls = sweep_class_of(cur_b & ((1u << log2_local) - 1u), log2_local);
-            cmask |= 1u << cls;
-            if (qn < (uint32_t)SUMMARY_RUNS) rcls |= (uint64_t)cls << (5u * qn);
+            cmask |= 1u << sweep_class_of(cur_b & ((1u << log2_local) - 1u), log2_local);
             if (qn < (uint32_t)SUMMARY_RUNS) {                          // 12 bits per run from bit 8 (kept in registers: LDS is what limits this kernel's occupancy)
                 const uint64_t fld = cur_nk | (cur_rel << 6);
                 const uint32_t b = 8u + 12u * qn;
@@ -386,7 +369,7 @@ partition_read(uint64_t r, uint32_t* smem, uint32_t* __restrict__ lh,
         // scatter), then 12 bits per run from bit 8
         const uint64_t lo = sum_lo | (qn <= (uint32_t)SUMMARY_RUNS ? qn : SUMMARY_OVERFLOW), hi = sum_hi;
         summaries[r] = uint4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
-        if (read_classes) { read_classes[r] = cmask; if (uint64_t* rc_ = const_cast<uint64_t*>(run_classes_of(read_classes, n_reads))) rc_[r] = rcls; }
+        if (read_classes) read_classes[r] = cmask;
         // a read with more runs than a summary holds goes on the list of reads the scanning scatter handles (two in
         // 10^5; in the counting scan `bucket_cur` is that list's counter, `records` the list, `n_out` its capacity)
         if (qn > (uint32_t)SUMMARY_RUNS && bucket_cur) {
@@ -485,7 +468,7 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
         const uint32_t gl = r < n_reads ? good_len[r] : 0;
         const bool live = gl >= (uint32_t)K + 1;                         // Kmerizer::map: len < K+1 emits nothing (:153)
         uint32_t qn = 0, cmask = 0;
-        uint64_t sum_lo = 0, sum_hi = 0, rcls = 0;
+        uint64_t sum_lo = 0, sum_hi = 0;
         if (live) {
             const uint64_t bit0 = base_off[r] * 8;
             uint64_t wi = bit0 >> 5, filled_to = wi;
@@ -583,15 +566,13 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
                 const uint32_t nk = (uint32_t)(bfld + 12 <= 64 ? sum_lo >> bfld : bfld >= 64 ? sum_hi >> (bfld - 64) : (sum_lo >> bfld) | (sum_hi << (64 - bfld))) & 63u;
                 if (lh) { const uint32_t bin = class_bin(cb, pp); atomicAdd(&lh[bin], 1u); atomicAdd(&lh[(PART_CLASSES << pp.log2_world) + bin], nk); }
                 else atomicAdd(&bucket_acc[cb], (1ull << 32) | nk);
-                const uint32_t cls = sweep_class_of(cb & ((1u << log2_local) - 1u), log2_local);
-                cmask |= 1u << cls;
-                rcls |= (uint64_t)cls << (5u * i);
+                cmask |= 1u << sweep_class_of(cb & ((1u << log2_local) - 1u), log2_local);
             }
         }
         if (r < n_reads) {
             const uint64_t lo = sum_lo | (qn <= (uint32_t)SUMMARY_RUNS ? qn : SUMMARY_OVERFLOW);
             summaries[r] = uint4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)sum_hi, (uint32_t)(sum_hi >> 32)};
-            if (read_classes) { read_classes[r] = cmask; if (uint64_t* rc_ = const_cast<uint64_t*>(run_classes_of(read_classes, n_reads))) rc_[r] = rcls; }
+            if (read_classes) read_classes[r] = cmask;
         }
         if (qn > (uint32_t)SUMMARY_RUNS) {
             const unsigned long long at = atomicAdd(ovf_count, 1ull);
@@ -612,12 +593,11 @@ constexpr int SLICE_READS = 16;
 template <int K, bool EMIT, typename F>
 __device__ __forceinline__ void for_each_run_in_pass(uint64_t r, const uint8_t* __restrict__ packed, uint64_t packed_bytes,
                                                      const uint64_t* __restrict__ base_off, const PartParams& pp,
-                                                     const uint4* __restrict__ summaries, const uint64_t* __restrict__ run_classes, F&& f)
+                                                     const uint4* __restrict__ summaries, F&& f)
 {
     const uint4 sm = summaries[r];
     const uint32_t n = sm.x & 15u;
     if (n == 0 || n == SUMMARY_OVERFLOW) return;
-    const uint64_t rcls = run_classes ? run_classes[r] : 0ull;
     const uint32_t* words = reinterpret_cast<const uint32_t*>(packed);
     const uint64_t n_words = (packed_bytes + 3) >> 2;
     const uint64_t bit0 = base_off[r] * 8;
@@ -632,7 +612,6 @@ __device__ __forceinline__ void for_each_run_in_pass(uint64_t r, const uint8_t* 
             const int b = B0 + 12 * i;
             const uint32_t fld = (uint32_t)(b + 12 <= 64 ? lo >> b : b >= 64 ? hi >> (b - 64) : (lo >> b) | (hi << (64 - b))) & 0xFFFu;
             const uint32_t nk = fld & 63u, rel = fld >> 6;
-            if (run_classes && !((pp.class_mask >> ((uint32_t)(rcls >> (5 * i)) & 31u)) & 1u)) { s0 += nk; continue; }   // a run of a class this pass does not touch
             const uint64_t bo = bit0 + 2ull * (s0 + rel);
             const uint64_t wi = bo >> 5;
             const uint32_t w0 = words[wi], w1 = wi + 1 < n_words ? words[wi + 1] : 0u;
@@ -681,7 +660,7 @@ k_scatter_slices(const uint8_t* __restrict__ packed, uint64_t packed_bytes, cons
     __syncthreads();
     const uint32_t n = n_list;
     for (uint32_t i = threadIdx.x; i < n; i += 256)
-        for_each_run_in_pass<K, false>(r_block + list[i], packed, packed_bytes, base_off, pp, summaries, run_classes_of(read_classes, n_reads),
+        for_each_run_in_pass<K, false>(r_block + list[i], packed, packed_bytes, base_off, pp, summaries,
                                        [&](uint32_t, uint32_t, uint32_t, uint32_t owner, uint64_t, bool) { atomicAdd(&cnt[owner], 1u); });
     __syncthreads();
     if (threadIdx.x < world) {
@@ -697,7 +676,7 @@ k_scatter_slices(const uint8_t* __restrict__ packed, uint64_t packed_bytes, cons
         const uint64_t r = r_block + list[i];
         int32_t tag = -1;
         if (bc && (int64_t)r + pp.read_id0 >= ign_bc_below) tag = bc[r];
-        for_each_run_in_pass<K, true>(r, packed, packed_bytes, base_off, pp, summaries, run_classes_of(read_classes, n_reads),
+        for_each_run_in_pass<K, true>(r, packed, packed_bytes, base_off, pp, summaries,
             [&](uint32_t s0, uint32_t nk, uint32_t lb, uint32_t owner, uint64_t bit0, bool last) {
                 const uint64_t dst = at[owner] + atomicAdd(&cnt[owner], 1u);
                 // only the read's last run has no successor base (its last k-mer ends the trimmed read)
@@ -755,7 +734,7 @@ k_scatter_runs(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const 
         const uint64_t r = r_block + list[i];
         int32_t tag = -1;
         if (bc && (int64_t)r + pp.read_id0 >= ign_bc_below) tag = bc[r];
-        for_each_run_in_pass<K, true>(r, packed, packed_bytes, base_off, pp, summaries, run_classes_of(read_classes, n_reads),
+        for_each_run_in_pass<K, true>(r, packed, packed_bytes, base_off, pp, summaries,
             [&](uint32_t s0, uint32_t nk, uint32_t lb, uint32_t, uint64_t bit0, bool last) {
                 const uint64_t dst = atomicAdd(&bucket_cur[lb], 1ull);             // one random access for base and rank
                 // only the read's last run has no successor base (its last k-mer ends the trimmed read)
@@ -870,10 +849,6 @@ struct PhaseClock {
 #else
 #define PH(i) do { } while (0)
 #endif
-#ifdef DFK_PROBE_STATS   // experiment only: [0] loop iterations, [1] batches, [2] lane probes, [3] waits on a locked slot
-__device__ unsigned long long g_probe_stats[4];
-#endif
-
 // what the first insert that gave up in an HBM table looked like: {set, probe steps, waits on a locked slot, log2 slots}
 __device__ unsigned int g_big_fail[4];
 
@@ -888,13 +863,7 @@ __device__ __forceinline__ bool table_insert(uint32_t* __restrict__ keys, uint32
                                              uint32_t S, const Probe& A, uint32_t& n_claimed)
 {
     uint32_t state = A.active ? PS_PROBING : PS_IDLE, slot = A.slot, seen = 0, cost = 0, waits = 0;
-#ifdef DFK_PROBE_STATS
-    uint32_t dbg_iter = 0;
-#endif
     while (__ballot(state == PS_PROBING) != 0ull) {
-#ifdef DFK_PROBE_STATS
-        ++dbg_iter;
-#endif
         if (state == PS_PROBING) {
             uint32_t e = 0, r0, r1, r2, r3 = A.k3;
             if (LDS_TABLE) {
@@ -931,16 +900,6 @@ __device__ __forceinline__ bool table_insert(uint32_t* __restrict__ keys, uint32
             state = fin | ((uint32_t)(cost >= PROBE_LIMIT) << 1);        // PS_FOUND, PS_FAILED or PS_PROBING
         }
     }
-#ifdef DFK_PROBE_STATS
-    {
-        uint32_t pr = cost / PROBE_COST, sp = cost % PROBE_COST;
-        for (int d = 32; d > 0; d >>= 1) { pr += __shfl_down(pr, d, 64); sp += __shfl_down(sp, d, 64); }
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&g_probe_stats[0], (unsigned long long)dbg_iter); atomicAdd(&g_probe_stats[1], 1ull);
-            atomicAdd(&g_probe_stats[2], (unsigned long long)pr); atomicAdd(&g_probe_stats[3], (unsigned long long)sp);
-        }
-    }
-#endif
     if (!LDS_TABLE && state == PS_FAILED && atomicCAS(&g_big_fail[0], 0u, 1u) == 0u) {
         g_big_fail[1] = (cost - waits) / PROBE_COST; g_big_fail[2] = waits; g_big_fail[3] = 31u - (uint32_t)__clz(S);
     }
@@ -1003,117 +962,6 @@ __device__ __forceinline__ bool table_insert(uint32_t* __restrict__ keys, uint32
         }
     }
     return state != PS_FAILED;
-}
-
-// Two keys per lane, probed side by side (LDS tables only).  k_count's waves spend their time waiting, not issuing: a probe
-// is an LDS round trip (compare-and-swap + the key words) that the next step depends on, a batch of 64 keys takes 3.2 of
-// them in a row (the longest probe sequence of the wave), and at four waves per SIMD there is not enough else to run
-// meanwhile -- ten or twelve waves per workgroup count 8 / 15 % faster with the same instructions, and
-// taking two fifths of the extraction's instructions away (pair_second) changed nothing.  Here the round trips of two
-// batches overlap: one loop iteration issues both keys' LDS operations before it looks at either answer.  Both keys of a
-// lane may be the same k-mer (a homopolymer run) or hash to the same slot: the operations of a wave execute in order, so the
-// second key's compare-and-swap sees the first one's lock and comes back in the next iteration, as a key of another lane
-// would.
-template <int KW, int NBC>
-__device__ __forceinline__ bool table_insert2(uint32_t* __restrict__ keys, uint32_t* __restrict__ cnt,
-                                              uint32_t* __restrict__ ctxs, uint32_t* __restrict__ bcw,
-                                              uint32_t S, const Probe& A, const Probe& B, uint32_t& n_claimed)
-{
-    uint32_t sa = A.active ? PS_PROBING : PS_IDLE, sb = B.active ? PS_PROBING : PS_IDLE;
-    uint32_t slot_a = A.slot, slot_b = B.slot, seen_a = 0, seen_b = 0, cost_a = 0, cost_b = 0;
-    while (__ballot((sa == PS_PROBING) | (sb == PS_PROBING)) != 0ull) {
-        uint32_t ea = 0, a0 = 0, a1 = 0, a2 = 0, a3 = A.k3, eb = 0, b0 = 0, b1 = 0, b2 = 0, b3 = B.k3;
-        const bool pa = sa == PS_PROBING, pb = sb == PS_PROBING;
-        if (pa) {
-            __hip_atomic_compare_exchange_strong(&cnt[slot_a], &ea, CNT_LOCK, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            DFK_COMPILER_FENCE();
-            a0 = tld(&keys[slot_a]); a1 = tld(&keys[S + slot_a]); a2 = tld(&keys[2 * S + slot_a]);
-            if (KW == 4) a3 = tld(&keys[3 * S + slot_a]);
-        }
-        DFK_COMPILER_FENCE();
-        if (pb) {
-            __hip_atomic_compare_exchange_strong(&cnt[slot_b], &eb, CNT_LOCK, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            DFK_COMPILER_FENCE();
-            b0 = tld(&keys[slot_b]); b1 = tld(&keys[S + slot_b]); b2 = tld(&keys[2 * S + slot_b]);
-            if (KW == 4) b3 = tld(&keys[3 * S + slot_b]);
-        }
-        DFK_COMPILER_FENCE();
-        if (pa) {
-            const bool won = ea == 0u;
-            if (won) {
-                tst(&keys[slot_a], A.k0); tst(&keys[S + slot_a], A.k1); tst(&keys[2 * S + slot_a], A.k2);
-                if (KW == 4) tst(&keys[3 * S + slot_a], A.k3);
-                DFK_COMPILER_FENCE();
-                __hip_atomic_store(&cnt[slot_a], A.fp << 24, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            const uint32_t locked = ea == CNT_LOCK;
-            const uint32_t match = ((ea >> 24) == A.fp) & (a0 == A.k0) & (a1 == A.k1) & (a2 == A.k2) & (a3 == A.k3);
-            const uint32_t fin = (uint32_t)won | match;
-            n_claimed += (uint32_t)won;
-            seen_a |= ea & (0u - match);
-            cost_a += PROBE_COST - (PROBE_COST - 1u) * locked;
-            slot_a = (slot_a + (A.step & ((fin | locked) - 1u))) & (S - 1);
-            sa = fin | ((uint32_t)(cost_a >= PROBE_LIMIT) << 1);
-        }
-        DFK_COMPILER_FENCE();
-        if (pb) {
-            const bool won = eb == 0u;
-            if (won) {
-                tst(&keys[slot_b], B.k0); tst(&keys[S + slot_b], B.k1); tst(&keys[2 * S + slot_b], B.k2);
-                if (KW == 4) tst(&keys[3 * S + slot_b], B.k3);
-                DFK_COMPILER_FENCE();
-                __hip_atomic_store(&cnt[slot_b], B.fp << 24, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            const uint32_t locked = eb == CNT_LOCK;
-            const uint32_t match = ((eb >> 24) == B.fp) & (b0 == B.k0) & (b1 == B.k1) & (b2 == B.k2) & (b3 == B.k3);
-            const uint32_t fin = (uint32_t)won | match;
-            n_claimed += (uint32_t)won;
-            seen_b |= eb & (0u - match);
-            cost_b += PROBE_COST - (PROBE_COST - 1u) * locked;
-            slot_b = (slot_b + (B.step & ((fin | locked) - 1u))) & (S - 1);
-            sb = fin | ((uint32_t)(cost_b >= PROBE_LIMIT) << 1);
-        }
-    }
-    // count, context, barcode: as table_insert (the comments on saturation and barcodes are there)
-    auto found = [&](const Probe& P, uint32_t state, uint32_t slot, uint32_t seen) {
-        const bool high = state == PS_FOUND && (seen & CNT_MASK) >= CNT_HALF;
-        if (state == PS_FOUND && !high) atomicAdd(&cnt[slot], 1u);
-        unsigned long long todo = __ballot(high);
-        while (todo) {                                                        // (wave-uniform: `todo` is a ballot)
-            const int leader = __ffsll((long long)todo) - 1;
-            const uint32_t lslot = (uint32_t)__builtin_amdgcn_readlane((int)slot, leader);
-            const unsigned long long same = __ballot(high && slot == lslot) & todo;
-            if ((int)(threadIdx.x & 63) == leader) {
-                const uint32_t k = (uint32_t)__popcll(same);
-                uint32_t cur = tld(&cnt[slot]);
-                for (;;) {
-                    const uint32_t c0 = cur & CNT_MASK, c1 = c0 + k < CNT_MASK ? c0 + k : CNT_MASK;
-                    if (c1 == c0) break;
-                    if (__hip_atomic_compare_exchange_strong(&cnt[slot], &cur, (cur & ~CNT_MASK) | c1, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                             __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-                }
-            }
-            todo &= ~same;
-        }
-        if (state != PS_FOUND) return;
-        atomicOr(&ctxs[slot], P.ctx);
-        if (NBC > 0) {
-            if (P.tag == -1) atomicOr(&bcw[slot], BCW_MULTI);
-            else if (P.tag > 0) {
-                bool settled = false;
-#pragma unroll
-                for (int j = 0; j < NBC; ++j)
-                    if (!settled) {
-                        const uint32_t old = atomicCAS(&bcw[(size_t)j * S + slot], 0u, (uint32_t)P.tag);
-                        settled = old == 0u || (old & ~BCW_MULTI) == (uint32_t)P.tag || (j == 0 && (old & BCW_MULTI));
-                    }
-                if (!settled) atomicOr(&bcw[slot], BCW_MULTI);
-            }
-        }
-    };
-    found(A, sa, slot_a, seen_a);
-    found(B, sb, slot_b, seen_b);
-    return sa != PS_FAILED && sb != PS_FAILED;
 }
 
 // One k-mer instance as read from the wave's staged chunk: header, barcode, the five payload words that
@@ -1211,145 +1059,13 @@ __device__ __forceinline__ uint32_t wave_count_chunk(const uint4* __restrict__ r
         // (every key word goes into the selector: the k-mers of a hot bucket share their minimizer, often at the
         // same offset, i.e. whole words of the key)
         if (SUB) A.active = A.active && ((((A.k0 * 0x9E3779B1u) ^ (A.k1 * 0x85EBCA77u) ^ (A.k2 * 0xC2B2AE3Du) ^ (A.k3 * 0x27D4EB2Fu)) >> 24) & sel_mask) == sel;
-#ifdef DFK_ABLATE_INSERT        // timing experiment only: keep the extraction alive, skip the table
-        if ((A.k0 ^ A.k1 ^ A.ctx) == 0x12345u) ++n_claimed;
-#else
         ok = table_insert<KTraits<K>::KW, NBC, LDS_TABLE>(keys, cnt, ctxs, bcw, S, A, n_claimed) && ok;
-#endif
     }
     n_claimed = wave_sum(n_claimed);
     if (lane == 0 && n_claimed) atomicAdd(n_fill, n_claimed);
     if (!ok) atomicOr(overflow, 1u);
     wave_sync();
     return end_u - first_u;
-}
-
-// ---- two consecutive k-mers of a record per lane: an EXPERIMENT (round 4), built with -DDFK_PAIRS, parity green, NOT the
-// default -- measured on MI355X (tools/pairs_ab.sh, tools/pmc_sq.sh): k_count 963 ms per step as it is,
-// 982 ms with the pair extraction and two inserts one after the other (-DDFK_PAIRS -DDFK_PAIRS_SERIAL), 993 ms with the two
-// keys probed side by side (table_insert2).  The extraction block does shrink (127 vector instructions for two k-mers against
-// 2 x 111), but a k_count wave is parked on s_waitcnt / barriers for 57 % of its cycles and issues during 31 % (SQ_WAIT_ANY,
-// SQ_ACTIVE_INST_ANY): instructions are not what it is short of, and the side-by-side loop adds more of them (+11 % vector,
-// +23 % scalar: both keys' bookkeeping in every iteration) than the shorter chain of LDS round trips gives back.
-// Rebuilding a k-mer from the 2-bit stream is two fifths of the insert path's vector instructions (fetch ~12, extraction
-// ~99 of ~267 per 64 instances), and nearly half of THAT is the 128-bit group reversal that turns the stream into KMer's
-// big-endian order.  The k-mer that follows in the same record needs none of it: its forward value is the predecessor's
-// shifted by one base with the next base appended -- KMer::toSuccessor, kmers/KMer.h:189-201, which is how the reference's own
-// Kmerizer::map walks a read (BuildReadQGraph48.cc:148-165) -- and its reverse complement is the next window of the
-// complemented stream.  So a lane takes instances (2j, 2j+1) of a record: one fetch, one full extraction, one rolled one,
-// two inserts.  A record of nk k-mers takes ceil(nk/2) lane slots; with nk odd the last slot's second half is idle (one
-// insert slot in 2 nk: 2 % at the 12.8 k-mers a record holds on average).
-struct PairRegs { uint32_t hdr, tag, q; u128 X, F; };
-
-// Stage records as wave_stage_piece does, indexing PAIR SLOTS instead of instances: returns the number of slots staged.
-template <int K>
-__device__ __forceinline__ uint32_t wave_stage_pairs(const uint4* __restrict__ records, uint64_t rb, uint64_t re,
-                                                     WaveStage<K>* __restrict__ st, int lane)
-{
-    static_assert(COUNT_CHUNK == 32, "one uint4 per lane");
-    const uint64_t hidx = 2 * rb + lane;
-    uint4 v{0, 0, 0, 0};
-    if (hidx < 2 * re) v = records[hidx];
-    reinterpret_cast<uint4*>(st->rec)[lane] = v;
-    st->msk[lane] = 0;
-    wave_sync();
-    const uint32_t nk = lane < COUNT_CHUNK ? (st->rec[8 * lane] & 63u) : 0u;
-    const uint32_t np = (nk + 1u) >> 1;
-    const uint32_t incl = wave_incl_scan(np, lane);
-    const uint32_t start = incl - np;
-    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    if (lane < COUNT_CHUNK) st->starts[lane] = start;
-    if (np) atomicOr(&st->msk[start >> 5], 1u << (start & 31u));
-    wave_sync();
-    const uint32_t c0 = __popc(tld(&st->msk[lane]));
-    st->pc[lane] = wave_incl_scan(c0, lane) - c0;
-    wave_sync();
-    return total;
-}
-
-// first k-mer of pair slot t: the full extraction (as make_probe), keeping the window and the forward value for the second
-template <int K>
-__device__ __forceinline__ Probe pair_first(const WaveStage<K>* __restrict__ st, uint32_t t, uint32_t S, bool active, PairRegs* keep)
-{
-    const uint32_t w = t >> 5;
-    const uint32_t bits = tld(&st->msk[w]) & (0xFFFFFFFFu >> (31u - (t & 31u)));
-    const uint32_t r = st->pc[w] + __popc(bits) - 1u;
-    const uint32_t q = 2u * (t - st->starts[r]);
-    const uint32_t* rec = st->rec + 8 * r;
-    const uint32_t* p = rec + 2 + (q >> 4);
-    const uint32_t hdr = rec[0], p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3], p4 = p[4];
-    const uint32_t nk = hdr & 63u;
-    // bits [2q, 2q + 128) of the payload: pred, K bases, succ, and the base after it (K + 3 bases: 2K + 6 <= 126 bits)
-    const uint32_t sh = (2u * q) & 31u;
-    const uint32_t x0 = alignbit(p1, p0, sh), x1 = alignbit(p2, p1, sh), x2 = alignbit(p3, p2, sh), x3 = alignbit(p4, p3, sh);
-    const u128 X{(uint64_t)x0 | ((uint64_t)x1 << 32), (uint64_t)x2 | ((uint64_t)x3 << 32)};
-    const uint32_t pred = x0 & 3u;
-    const u128 ks = shr128(X, 2);
-    constexpr int SB = 2 * K + 2;
-    const uint32_t succ = (uint32_t)(SB >= 64 ? (X.hi >> (SB - 64)) : (X.lo >> SB)) & 3u;
-    const u128 m = KTraits<K>::mask();
-    const u128 R{~ks.lo & m.lo, ~ks.hi & m.hi};
-    const u128 rv{rev2_64(ks.hi), rev2_64(ks.lo)};
-    const u128 F = shr128(rv, 128 - KTraits<K>::BITS);                  // (the masked-off bases above the k-mer fall out at the bottom)
-    const bool rev = lt128(R, F);
-    uint32_t ctx = 0;
-    if (q > 0 || (hdr & 64u)) ctx |= 0x10u << pred;
-    if (q + 1 < nk || (hdr & 128u)) ctx |= 1u << succ;
-    if (rev) ctx = ctx_rc(ctx);
-    *keep = PairRegs{hdr, rec[1], q, X, F};
-    return probe_begin(rev ? R : F, ctx, (int32_t)rec[1], S, active);
-}
-
-// second k-mer of the slot: KMer::toSuccessor on the forward value, the next window of the complemented stream
-template <int K>
-__device__ __forceinline__ Probe pair_second(const PairRegs& k, uint32_t S, bool active)
-{
-    const uint32_t nk = k.hdr & 63u, q = k.q + 1u;
-    const u128 m = KTraits<K>::mask();
-    constexpr int SB = 2 * K + 2;
-    const uint32_t base_in = (uint32_t)(SB >= 64 ? (k.X.hi >> (SB - 64)) : (k.X.lo >> SB)) & 3u;       // the first k-mer's successor
-    const uint32_t succ = (uint32_t)(SB + 2 >= 64 ? (k.X.hi >> (SB + 2 - 64)) : (k.X.lo >> (SB + 2))) & 3u;
-    const uint32_t pred = (uint32_t)(k.X.lo >> 2) & 3u;                  // the first k-mer's first base
-    const u128 ks = shr128(k.X, 4);
-    const u128 R{~ks.lo & m.lo, ~ks.hi & m.hi};
-    u128 F = shl128(k.F, 2); F.lo |= base_in; F.lo &= m.lo; F.hi &= m.hi;
-    const bool rev = lt128(R, F);
-    uint32_t ctx = 0x10u << pred;                                        // (q >= 1: there is a predecessor in the record)
-    if (q + 1 < nk || (k.hdr & 128u)) ctx |= 1u << succ;
-    if (rev) ctx = ctx_rc(ctx);
-    return probe_begin(rev ? R : F, ctx, (int32_t)k.tag, S, active && q < nk);
-}
-
-template <int K, int NBC, bool SUB>
-__device__ __forceinline__ void wave_count_chunk_pairs(const uint4* __restrict__ records, uint64_t rb, uint64_t re,
-                                                       WaveStage<K>* __restrict__ st, int lane,
-                                                       uint32_t* keys, uint32_t* cnt, uint32_t* ctxs, uint32_t* bcw,
-                                                       uint32_t S, uint32_t* n_fill, uint32_t* overflow, uint32_t sub)
-{
-    const uint32_t sel_mask = (1u << (sub >> 8)) - 1u, sel = sub & 0xFFu;
-    auto selected = [&](const Probe& A) { return ((((A.k0 * 0x9E3779B1u) ^ (A.k1 * 0x85EBCA77u) ^ (A.k2 * 0xC2B2AE3Du) ^ (A.k3 * 0x27D4EB2Fu)) >> 24) & sel_mask) == sel; };
-    const uint32_t total = wave_stage_pairs<K>(records, rb, re, st, lane);
-    bool ok = true;
-    uint32_t n_claimed = 0;
-    const uint32_t end_u = __builtin_amdgcn_readfirstlane(total);       // scalar loop control
-    for (uint32_t t0 = 0; t0 < end_u; t0 += 64) {
-        const uint32_t t = t0 + lane;
-        PairRegs keep;
-        Probe A = pair_first<K>(st, min(t, end_u - 1u), S, t < end_u, &keep);
-        if (SUB) A.active = A.active && selected(A);
-        Probe B = pair_second<K>(keep, S, t < end_u);
-        if (SUB) B.active = B.active && selected(B);
-#ifdef DFK_PAIRS_SERIAL
-        ok = table_insert<KTraits<K>::KW, NBC, true>(keys, cnt, ctxs, bcw, S, A, n_claimed) && ok;
-        ok = table_insert<KTraits<K>::KW, NBC, true>(keys, cnt, ctxs, bcw, S, B, n_claimed) && ok;
-#else
-        ok = table_insert2<KTraits<K>::KW, NBC>(keys, cnt, ctxs, bcw, S, A, B, n_claimed) && ok;
-#endif
-    }
-    n_claimed = wave_sum(n_claimed);
-    if (lane == 0 && n_claimed) atomicAdd(n_fill, n_claimed);
-    if (!ok) atomicOr(overflow, 1u);
-    wave_sync();
 }
 
 constexpr int BIG_TICKET_CHUNKS = 4;                 // chunks a wave takes per ticket
@@ -1656,11 +1372,7 @@ __device__ __forceinline__ uint32_t table_finish(uint32_t* keys, uint32_t* cnt, 
         }
     }
     // ---- pass 2
-#ifdef DFK_ABLATE_PASS2
-    if (false) {
-#else
     if (cp.do_adj) {
-#endif
         const uint32_t total = __builtin_amdgcn_readfirstlane(tld(n_tasks));
         if (total <= ADJ_TASKS) {
             for (uint32_t t = tid; t < total; t += nthreads) resolve(tasks[t]);
@@ -1714,11 +1426,7 @@ __device__ __forceinline__ uint32_t table_finish(uint32_t* keys, uint32_t* cnt, 
         const uint32_t used = __builtin_amdgcn_readfirstlane(tld(&ctl[CTL_USED]));
         const unsigned long long cur = uniform64(tld(&ctl[CTL_OUT_LO]), tld(&ctl[CTL_OUT_HI]));
         const unsigned long long nxt = uniform64(tld(&ctl[CTL_NEXT_LO]), tld(&ctl[CTL_NEXT_HI]));
-#ifdef DFK_ABLATE_EMIT
-        for (uint32_t i = tid; i < 0 * ns; i += nthreads) {
-#else
         for (uint32_t i = tid; i < ns; i += nthreads) {
-#endif
             const uint32_t slot = solid_list[i];
             const uint32_t pos = used + i;
             emit(slot, tld(&cnt[slot]), tld(&bcw[slot]), pos < OUT_CHUNK ? cur + pos : nxt + (pos - OUT_CHUNK));
@@ -1842,13 +1550,8 @@ k_count(const uint4* __restrict__ records, const ItemRange* __restrict__ items, 
         } else
         for (uint32_t at = w_lo; at < w_hi; at += COUNT_CHUNK) {
             if (__builtin_amdgcn_readfirstlane(tld(&ctl[CTL_OVF]))) break;
-#ifndef DFK_PAIRS
             wave_count_chunk<K, NBC, true, SUB>(records, rb + at, rb + w_hi, st, lane, keys, cnt, ctxs, bcw, S,
                                              &ctl[CTL_FILL], &ctl[CTL_OVF], sub);
-#else           // experiment, measured and not kept (below): two consecutive k-mers per lane, -DDFK_PAIRS_SERIAL or probed side by side
-            wave_count_chunk_pairs<K, NBC, SUB>(records, rb + at, rb + w_hi, st, lane, keys, cnt, ctxs, bcw, S,
-                                                &ctl[CTL_FILL], &ctl[CTL_OVF], sub);
-#endif
             if (lane == 0 && tld(&ctl[CTL_FILL]) > (S / 4) * 3) tst(&ctl[CTL_OVF], 1u);   // stop when 3/4 full
         }
         PH(2);
@@ -1870,14 +1573,7 @@ k_count(const uint4* __restrict__ records, const ItemRange* __restrict__ items, 
             for (uint32_t i = tid; i < (3 + XW) * S; i += NT) cnt[i] = 0;   // abandon the table
             __syncthreads();                                           // everyone has read CTL_OVF before it is reset
         } else {
-#ifdef DFK_ABLATE_FINISH        // timing experiment only: no solidity/adjacency/emit passes
-            for (uint32_t i = tid; i < (3 + XW) * S; i += NT) cnt[i] = 0;
-            uint32_t occ = 0;
-            if (false)
-#else
-            uint32_t occ =
-#endif
-            table_finish<K, NBC, S / 2>(keys, cnt, ctxs, bcw, S, cp, seg_out, ctl, &g->part_cursor,
+            uint32_t occ = table_finish<K, NBC, S / 2>(keys, cnt, ctxs, bcw, S, cp, seg_out, ctl, &g->part_cursor,
                                                          &g->solid_overflow, hist, hist_global, tasks, &ctl[CTL_NTASK],
                                                          &ctl[CTL_BOUNDARY], solid_list, &ctl[CTL_NSOLID], tid, NT
 #ifdef DFK_PHASE_TIMES
@@ -2369,7 +2065,9 @@ __device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t* sc
     return off + incl - v;
 }
 
-// The same regroup without a global atomic: two levels of counting sort, all counters in LDS.
+// Regroup of received records: after the all-to-all a rank holds the records it owns from every peer, in arrival order,
+// and items must be ranges of whole fine buckets, so the records are scattered once more by the fine bucket id kept in
+// their header -- without a global atomic: two levels of counting sort, all counters in LDS.
 //   level 1  RG_PARTS partitions by the top bits of the bucket id.  A block owns a contiguous chunk of the input:
 //            it counts its records per partition (k_rg_hist), a device scan of the [partition][block] counts gives
 //            every block its own write position in every partition, and the block copies its records there
@@ -2563,27 +2261,6 @@ k_adj_apply(uint4* __restrict__ entries, const uint64_t* __restrict__ src, const
     uint32_t* word = reinterpret_cast<uint32_t*>(entries + 2 * (s >> 3) + 1) + 1;    // count_ctx
     atomicAnd(word, ~(1u << (24 + (uint32_t)(s & 7))));
 }
-
-// ============================================================================ multi-GPU: regroup received records
-// After the all-to-all a rank holds the records it owns from every peer, in arrival order.
-// Items must be ranges of whole fine buckets, so scatter them once more by the fine bucket id
-// kept in the header (pure 32-byte record moves).
-template <bool WRITE>
-__global__ void __launch_bounds__(256)
-k_regroup(const uint4* __restrict__ in, uint64_t n, uint32_t local_mask, unsigned long long* __restrict__ bucket_acc,
-          const uint64_t* __restrict__ bucket_base, uint32_t* __restrict__ bucket_cur, uint4* __restrict__ out)
-{
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint4 a = in[2 * i];
-    uint32_t b = (a.x >> 8) & local_mask;
-    if (!WRITE) atomicAdd(&bucket_acc[b], (1ull << 32) | (a.x & 63u));
-    else {
-        uint64_t dst = bucket_base[b] + atomicAdd(&bucket_cur[b], 1u);
-        out[2 * dst] = a; out[2 * dst + 1] = in[2 * i + 1];
-    }
-}
-
 
 // Reads whose run summary overflowed (more than SUMMARY_RUNS runs), in ascending order: they go through the
 // scanning scatter, lane per read, so the list must be dense.

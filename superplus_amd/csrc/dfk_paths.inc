@@ -635,7 +635,7 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
                     HIP_TRY(hipStreamSynchronize(c->stream));
                     std::vector<FilePiece> pieces;
                     for (uint64_t o = 0; o < 8 * n_r; o += XFER_CHUNK) pieces.push_back(FilePiece{(const char*)wide + o, std::min<uint64_t>(XFER_CHUNK, 8 * n_r - o), 24 + 8 * h_first[e0] + o});
-                    const bool mapped = had >= var_tab && !getenv("DFK_NO_INV_MAP");     // the lists' pages exist: through a mapping
+                    const bool mapped = had >= var_tab;     // the lists' pages exist: through a mapping
                     const uint64_t m_lo = 24 + 8 * h_first[e0], m_hi = m_lo + 8 * n_r;
                     if (tail) {
                         tail->fd = fd; fd = -1;

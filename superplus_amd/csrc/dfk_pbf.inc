@@ -114,7 +114,7 @@ int pbf_run(dfk_ctx* c, const dfk_pbf_input* in, dfk_pbf* R)
             HIP_TRY(hipStreamSynchronize(c->stream));
             c->release(ssz);
             if ((rc = c->alloc(B.scratch, std::max<uint64_t>(1, words) * 4, "encoder scratch", true))) return rc;
-            if (std::max(max_len[0], max_len[1]) <= PBF_LDS_LEN && !getenv("DFK_PBF_NO_LDS"))
+            if (std::max(max_len[0], max_len[1]) <= PBF_LDS_LEN)
                 hipLaunchKernelGGL(k_pbf_pq_plan_lds, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((B.nk + 63) / 64, 64ull * cus))), dim3(64), 0, c->stream, F, order, B.k0, B.nk,
                                    (const uint64_t*)B.soff.p, (uint32_t*)B.scratch.p, (uint32_t*)B.nblk.p, (uint64_t*)pq_sz.p + B.k0, bad);
             else

@@ -189,36 +189,20 @@ int shard_count_typed(dfk_ctx* c, const void* d_records, uint64_t n_records, uin
     const uint32_t l2_local = c->shard_log2_nb - lw - S->log2_pass;
     const uint64_t nb = 1ull << l2_local;
     // regroup by fine bucket -- two levels of counting sort with LDS counters (k_rg_*), no global atomics; booked
-    // as partition time.  (DFK_REGROUP_ATOMICS=1: the one-level version, a global atomic per record and phase.)
+    // as partition time.
     Timer t_regroup(c->stream);
     t_regroup.start();
-    static const bool use_atomics = getenv("DFK_REGROUP_ATOMICS") != nullptr;
     if (l2_local > 24) return fail(DFK_E_ARG, "a pass of 2^%u buckets per rank: the record header keeps 24 bits", l2_local);
     DevBuf acc; int rc = c->alloc(acc, nb * 8, "regroup counters"); if (rc) return rc;
     Partition P;
     const uint64_t budget = item_budget<K>(c);
     DevBuf* mine = nullptr;                                              // the receive buffer, if it is the library's
     for (DevBuf& rb : c->shard_recv) if (rb.p && d_records == rb.p) mine = &rb;
-    if (use_atomics || n_records == 0) {
+    if (n_records == 0) {                                                // nothing received: empty tables, no kernel
         HIP_TRY(hipMemsetAsync(acc.p, 0, nb * 8, c->stream));
-        const unsigned grid = (unsigned)((n_records + 255) / 256);
-        if (grid)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_regroup<false>), dim3(grid), dim3(256), 0, c->stream, (const uint4*)d_records, n_records,
-                               (uint32_t)(nb - 1), (unsigned long long*)acc.p, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint4*)nullptr);
-        HIP_TRY(hipGetLastError());
         rc = pass_tables(c, acc, l2_local, 1, 0, (uint32_t)nb, budget, &P); if (rc) return rc;
         c->release(acc);
-        if (P.n_records != n_records) return fail(DFK_E_HIP, "regroup lost records");
-        DevBuf cur;
-        rc = c->alloc(cur, nb * 4, "regroup cursors"); if (rc) return rc;
-        rc = c->alloc(P.records, n_records * 32, "regrouped records"); if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(cur.p, 0, nb * 4, c->stream));
-        if (grid)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_regroup<true>), dim3(grid), dim3(256), 0, c->stream, (const uint4*)d_records, n_records,
-                               (uint32_t)(nb - 1), (unsigned long long*)nullptr, (const uint64_t*)P.base.p, (uint32_t*)cur.p, (uint4*)P.records.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->release(cur);
+        rc = c->alloc(P.records, 0, "regrouped records"); if (rc) return rc;
     } else {
         const uint32_t part_shift = l2_local > RG_LOG2_PARTS ? l2_local - RG_LOG2_PARTS : 0;
         const uint32_t n_parts = (uint32_t)(nb >> part_shift);

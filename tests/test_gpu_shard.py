@@ -54,6 +54,33 @@ def test_sharded_equals_single(oracle, world, K, ign, passes, pipelined):
     assert sum(d.stats()["n_distinct"] for d in ranks) == ref["n_distinct"]
 
 
+@pytest.mark.parametrize("pipelined", [False, True])
+def test_sharded_pass_with_nothing_received(oracle, pipelined):
+    """Ranks that receive no records in a pass build empty tables for it and leave the count to the others.  Every read
+    is the same 100 bases: their k-mers have four minimizers, so at most four of the eight ranks own any of them."""
+    from superplus_amd.dist import DistDfk, run_inprocess
+    src = util.make_set(23, 700, 300, err=0.0)
+    n, nb, nq = src["n_reads"], int(src["base_off"][1]), int(src["pq_off"][1])
+    rs = dict(packed=np.tile(src["packed"][:nb], n), base_off=np.arange(n + 1, dtype=np.uint64) * np.uint64(nb),
+              read_len=np.full(n, src["read_len"][0], np.uint32), pq_bytes=np.tile(src["pq_bytes"][:nq], n),
+              pq_off=np.arange(n + 1, dtype=np.uint64) * np.uint64(nq), bc=src["bc"], n_reads=n)
+    ref = oracle.run(rs["packed"], rs["base_off"], rs["read_len"], rs["pq_bytes"], rs["pq_off"], rs["bc"], K=48)
+    dev = torch.device("cuda", 0)
+    ranks = [DistDfk(K=48, device=0) for _ in range(8)]
+    received = []
+    for d in ranks:
+        count = d.count_records
+        d.count_records = lambda recv, pass_=0, count=count: (received.append(recv.numel() // 32), count(recv, pass_))[1]
+    run_inprocess(ranks, _shards(rs, 8, dev), pipelined=pipelined)
+    assert min(received) == 0 and sum(received) > 0 and ref["n_solid"] > 0
+    allk = np.concatenate([d.solid() for d in ranks])
+    util.assert_same_solid(allk[np.lexsort((allk["w1"], allk["w0"]))], ref["solid"], "pass with nothing received")
+    hist = np.zeros(len(ref["hist"]), np.int64)
+    for d in ranks:
+        h = d.spectrum(); hist[: len(h)] += h
+    assert np.array_equal(hist, ref["hist"])
+
+
 def test_sharded_long_reads(oracle):
     """Reads whose summaries overflow reach their owners through the scanning scatter's slice mode."""
     from superplus_amd.dist import DistDfk, run_inprocess
