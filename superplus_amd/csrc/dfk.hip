@@ -431,6 +431,11 @@ int table_totals(dfk_ctx* c, const DevBuf& acc, uint64_t nb, uint64_t* n_records
 struct ScanJob {
     PartParams pp; uint64_t nb = 0, n_bins = 0, ovf_cap = 0; bool by_class = false, ranged = false;
     DevBuf ovf_tmp, d_n;
+    // the register scan's run keys (k_scan_count<K, 16, true>): class slices, their partition into sub-slices, and per
+    // sub-slice totals | offsets | cursors -- all scratch, counted a piece of at most piece_reads reads at a time
+    bool keyed = false; uint32_t n_cls = 0, n_sub = 0, sb = 0; uint64_t piece_reads = 0;
+    ScanKeys sk{};
+    DevBuf keys, keys2, fill, sub;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;                  // a pair per launch: ms_part_count is their sum
     ~ScanJob() { for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } }
 };
@@ -456,6 +461,70 @@ int scan_begin(dfk_ctx* c, const Inputs& in, uint32_t log2_world, int64_t read_i
     rc = c->alloc(J->ovf_tmp, J->ovf_cap * 4, "overflow read list (scratch)"); if (rc) return rc;
     rc = c->alloc(J->d_n, 16, "overflow read count"); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(J->d_n.p, 0, 16, c->stream));
+    // keys a read makes: its first run and about two per W + 1 k-mers (random minimizers).  The keys pay where that is
+    // four or more (at 2 x 100 bp: K=40, 5.7 runs a read, the scan 505 -> 409 ms; K=48, 4.1, 368 -> 333); at K=60 (2.8)
+    // the counting kernels cost more than the atomics they replace (284 -> 313 ms), and the scan keeps its atomics
+    const double runs = in.n_reads ? 1.0 + 2.0 * std::max(0.0, 4.0 * (double)in.packed_bytes / (double)in.n_reads - K + 1) / (J->pp.W + 1) : 0.0;
+    J->keyed = !by_class && scan_takes_ranges<K>(c) && in.n_reads && (runs >= 3.5 || getenv("DFK_SCAN_KEY_PIECE"));
+    if (J->keyed) {
+        const uint32_t lb = T->log2_nb, cb = std::min<uint32_t>(6, lb);
+        J->sk.ib = lb - cb; J->n_cls = 1u << cb;
+        J->sb = std::min(KEY_SUB_BITS, J->sk.ib); J->n_sub = 1u << (J->sk.ib - J->sb);
+        // a quarter to spare for reads longer than the mean and classes fuller than the mean (what still does not fit is
+        // counted by the global atomic)
+        const double per_read = 1.25 * runs;
+        // two copies of the keys (slices, partition); at most a third of what the arena can still give, and never more than
+        // KEY_SCRATCH_MAX, so that the pass plan after scan_end finds the arena as it was
+        constexpr uint64_t KEY_SCRATCH_MAX = 16ull << 30;
+        const uint64_t want = 8ull * (uint64_t)(per_read * (double)in.n_reads) + 8ull * J->n_cls;
+        const uint64_t room = std::min<uint64_t>(std::min(want, KEY_SCRATCH_MAX), c->largest_allocatable() / 3);
+        J->sk.cap = std::max<uint64_t>(1024, room / 8 / J->n_cls);
+        J->piece_reads = std::max<uint64_t>(PART_THREADS, (uint64_t)((double)(J->sk.cap * J->n_cls) / per_read));
+        if (const char* e = getenv("DFK_SCAN_KEY_PIECE")) J->piece_reads = std::max<uint64_t>(1, std::min<uint64_t>(J->piece_reads, strtoull(e, nullptr, 10)));
+        const uint64_t n_subs = (uint64_t)J->n_cls * J->n_sub;
+        rc = c->alloc(J->keys, J->sk.cap * J->n_cls * 4, "run keys (scratch)"); if (rc) return rc;
+        rc = c->alloc(J->keys2, J->sk.cap * J->n_cls * 4, "run keys by sub-slice (scratch)"); if (rc) return rc;
+        rc = c->alloc(J->fill, J->n_cls * 8, "run key slice fills (scratch)"); if (rc) return rc;
+        rc = c->alloc(J->sub, (3 * n_subs + 1) * 8, "run key sub-slices (scratch)"); if (rc) return rc;
+        J->sk.keys = (uint32_t*)J->keys.p; J->sk.fill = (unsigned long long*)J->fill.p;
+        TRACE("run keys: %u classes of %llu keys, %u sub-slices each, pieces of %llu reads", J->n_cls, (unsigned long long)J->sk.cap,
+              J->n_sub, (unsigned long long)J->piece_reads);
+    }
+    return 0;
+}
+
+// the counting scan over reads [r0, r1) with run keys, then the keys counted into bucket_acc
+template <int K>
+int scan_keys_piece(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, uint64_t r0, uint64_t r1)
+{
+    static const unsigned scan_blocks = getenv("DFK_SCAN_BLOCKS") ? (unsigned)atoi(getenv("DFK_SCAN_BLOCKS")) : 0;
+    const unsigned cus = (unsigned)c->prop.multiProcessorCount;
+    const unsigned grid = (unsigned)std::min<uint64_t>((r1 - r0 + PART_THREADS - 1) / PART_THREADS, (uint64_t)(scan_blocks ? scan_blocks : 128u) * cus);
+    const uint64_t n_subs = (uint64_t)J->n_cls * J->n_sub;
+    auto* cnt = (unsigned long long*)J->sub.p;
+    auto* off = cnt + n_subs;
+    auto* cur = off + n_subs + 1;
+    HIP_TRY(hipMemsetAsync(J->fill.p, 0, J->n_cls * 8, c->stream));
+    HIP_TRY(hipMemsetAsync(cnt, 0, n_subs * 8, c->stream));
+    const size_t lds = sizeof(uint32_t) * (PART_RING + SUMMARY_RUNS) * PART_THREADS + SCAN_STAGE_LDS;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, true>), dim3(grid), dim3(PART_THREADS), lds, c->stream,
+                       in.packed, in.packed_bytes, in.base_off, (const uint32_t*)c->good_len.p, r0, r1, J->pp,
+                       (unsigned long long*)T->acc.p, (unsigned long long*)nullptr, (unsigned long long*)J->d_n.p, J->ovf_cap,
+                       (uint32_t*)J->ovf_tmp.p, (uint4*)T->summ.p, (uint32_t*)T->classes.p, J->sk);
+    HIP_TRY(hipGetLastError());
+    const dim3 per_class(std::max(1u, 16u * cus / J->n_cls), J->n_cls);
+    const uint32_t sh = 6 + J->sb;
+    hipLaunchKernelGGL(k_keys_subcount, per_class, dim3(256), J->n_sub * 4, c->stream,
+                       (const uint32_t*)J->keys.p, (const unsigned long long*)J->fill.p, J->sk.cap, sh, J->n_sub, cnt);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_keys_offsets, dim3(1), dim3(1024), 0, c->stream, (const unsigned long long*)cnt, (uint32_t)n_subs, off, cur);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_keys_partition, per_class, dim3(256), J->n_sub * 12, c->stream,
+                       (const uint32_t*)J->keys.p, (const unsigned long long*)J->fill.p, J->sk.cap, sh, J->n_sub, cur, (uint32_t*)J->keys2.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_keys_count, dim3((unsigned)n_subs), dim3(1024), 0, c->stream,
+                       (const uint32_t*)J->keys2.p, (const unsigned long long*)off, J->sb, (unsigned long long*)T->acc.p);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -476,12 +545,16 @@ int scan_range(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, uint64_
     HIP_TRY(hipEventRecord(e0, c->stream));
     // the minimizer length everybody uses gets the scan whose window lives in registers (all three K since the positions are
     // packed four to a register); other lengths the general one
-    if (scan_takes_ranges<K>(c)) {
+    if (J->keyed) {
+        for (uint64_t p0 = r0; p0 < r1; p0 += J->piece_reads) {
+            int rc = scan_keys_piece<K>(c, in, T, J, p0, std::min(r1, p0 + J->piece_reads)); if (rc) return rc;
+        }
+    } else if (scan_takes_ranges<K>(c)) {
         const size_t lds_r = sizeof(uint32_t) * (PART_RING + SUMMARY_RUNS) * PART_THREADS + (by_class ? J->n_bins * 4 : 0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16>), dim3(grid), dim3(PART_THREADS), lds_r, c->stream,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, false>), dim3(grid), dim3(PART_THREADS), lds_r, c->stream,
                            in.packed, in.packed_bytes, in.base_off, (const uint32_t*)c->good_len.p, r0, r1, pp,
                            (unsigned long long*)T->acc.p, (unsigned long long*)T->class_hist.p, (unsigned long long*)J->d_n.p, J->ovf_cap,
-                           (uint32_t*)J->ovf_tmp.p, (uint4*)T->summ.p, (uint32_t*)T->classes.p);
+                           (uint32_t*)J->ovf_tmp.p, (uint4*)T->summ.p, (uint32_t*)T->classes.p, ScanKeys{});
     } else {
         if (r0 != 0 || r1 != in.n_reads) return fail(DFK_E_STATE, "the general scan takes every read at once");
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_partition<K, false>), dim3(grid), dim3(PART_THREADS), lds_a, c->stream,
@@ -500,6 +573,7 @@ int scan_end(dfk_ctx* c, const Inputs& in, uint64_t n_inst, BucketTable* T, Scan
 {
     int rc = 0;
     T->n_ovf = 0;
+    c->release(J->keys); c->release(J->keys2); c->release(J->fill); c->release(J->sub);   // (stream-ordered: the counting is queued)
     if (in.n_reads) {
         HIP_TRY(hipMemcpyAsync(&T->n_ovf, J->d_n.p, 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));

@@ -437,18 +437,37 @@ __device__ __forceinline__ void static_for(F&& f)
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
 }
 
-template <int K, int M>
+// ---- run keys: the counting scan's per-bucket totals without a global atomic per run
+// A 64-bit atomic per run on the 1-GB table runs at the memory side's rate for random atomics (19 G/s, 24 G/s on windows
+// of 2-128 MB: tools/microbench_xcd_atomics.hip), which was the scan's whole time.  Instead each run becomes a 32-bit KEY,
+// (bucket within its class << 6) | nk, in the slice of its class (the table's top min(6, log2_nb) bits): the scan stages
+// keys in LDS and flushes them with one reservation per class present.  Then, per piece of reads: the sub-slices' totals
+// (k_keys_subcount), their offsets (k_keys_offsets), a partition of every class slice into sub-slices of 2^KEY_SUB_BITS
+// buckets (k_keys_partition), and per sub-slice an LDS table ADDED into bucket_acc (k_keys_count).  Keys that find their
+// class slice full are counted with the old global atomic on the spot, so the result never depends on the room given.
+struct ScanKeys {
+    uint32_t* keys;                   // [n_cls][cap] keys of each class
+    unsigned long long* fill;         // [n_cls] keys reserved in each class slice (may pass cap: the rest were counted directly)
+    uint64_t cap;                     // room of a class slice
+    uint32_t ib;                      // bits of a bucket within its class: log2_nb - min(6, log2_nb)
+};
+constexpr int SCAN_STAGE = 1792;      // keys a scan block stages (5 B each): with the scan's own 6 KB, 16 KB -- ten blocks a CU at K=40
+constexpr uint32_t KEY_SUB_BITS = 14; // buckets of a sub-slice: 2^14 u64 counters = 128 KB of LDS
+constexpr uint32_t KEY_TILE = 16384;  // keys a partition block reserves room for at once (one atomic per sub-slice present)
+
+template <int K, int M, bool KEYS>
 __global__ void __launch_bounds__(PART_THREADS)
 k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const uint64_t* __restrict__ base_off,
              const uint32_t* __restrict__ good_len, uint64_t r_first, uint64_t n_reads /* reads [r_first, n_reads) */, PartParams pp,
              unsigned long long* __restrict__ bucket_acc, unsigned long long* __restrict__ class_hist,
              unsigned long long* __restrict__ ovf_count, uint64_t ovf_cap, uint32_t* __restrict__ ovf_list,
-             uint4* __restrict__ summaries, uint32_t* __restrict__ read_classes)
+             uint4* __restrict__ summaries, uint32_t* __restrict__ read_classes, ScanKeys sk)
 {
     constexpr int W = K - M + 1;
     constexpr uint32_t mmask = M == 16 ? 0xFFFFFFFFu : ((1u << (2 * M)) - 1u);
     constexpr uint32_t rsh = 2 * (M - 1);
     constexpr int RUNS = SUMMARY_RUNS;                                   // buckets a lane remembers per read: as many as a summary holds
+    static_assert(KTraits<K>::NK_MAX < 64, "nk takes the key's six low bits");
     extern __shared__ uint32_t smem[];
     uint32_t* ring = smem;                                               // [PART_RING][PART_THREADS] words of the read
     uint32_t* runb = smem + PART_RING * PART_THREADS;                    // [RUNS][PART_THREADS] bucket of each closed run
@@ -460,6 +479,33 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
         __syncthreads();
     }
     const int tid = threadIdx.x;
+    // KEYS: staged keys, their classes, per class the count staged and the room reserved for them in its slice
+    uint32_t* st_key = runb + RUNS * PART_THREADS;
+    unsigned long long* st_base = reinterpret_cast<unsigned long long*>(st_key + SCAN_STAGE);
+    uint32_t* st_h = reinterpret_cast<uint32_t*>(st_base + PART_CLASSES);
+    uint32_t* st_n = st_h + PART_CLASSES;
+    uint8_t* st_cls = reinterpret_cast<uint8_t*>(st_n + 1);
+    const uint32_t n_cls = 1u << (pp.log2_nb - sk.ib);
+    if constexpr (KEYS) {
+        if (tid < PART_CLASSES) st_h[tid] = 0;
+        if (tid == 0) *st_n = 0;
+        __syncthreads();
+    }
+    auto flush = [&]() {                                                 // (block-uniform; after a barrier)
+        const uint32_t n = *st_n;
+        if (tid < (int)n_cls) { const uint32_t h = st_h[tid]; if (h) st_base[tid] = atomicAdd(&sk.fill[tid], (unsigned long long)h); st_h[tid] = 0; }
+        __syncthreads();
+        for (uint32_t j = tid; j < n; j += PART_THREADS) {
+            const uint32_t key = st_key[j], cls = st_cls[j];
+            const unsigned long long at = st_base[cls] + atomicAdd(&st_h[cls], 1u);
+            if (at < sk.cap) sk.keys[cls * sk.cap + at] = key;
+            else atomicAdd(&bucket_acc[(cls << sk.ib) | (key >> 6)], (1ull << 32) | (key & 63u));   // its slice is full
+        }
+        __syncthreads();
+        if (tid < (int)n_cls) st_h[tid] = 0;
+        if (tid == 0) *st_n = 0;
+        __syncthreads();
+    };
     const uint32_t* words = reinterpret_cast<const uint32_t*>(packed);
     const uint64_t n_words = (packed_bytes + 3) >> 2;
     const uint32_t log2_local = pp.log2_nb - pp.log2_world;
@@ -558,15 +604,39 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
             close_run();
         }
         // ---- the runs' buckets: counters and class mask, all lanes together (a read has ~4 runs)
+        // (KEYS: the whole block walks the runs together, so that a full stage can be flushed between two of them)
         const uint32_t mine = min(qn, (uint32_t)RUNS);
-        for (uint32_t i = 0; __ballot(i < mine) != 0ull; ++i) {
-            if (i < mine) {
-                const uint32_t cb = runb[i * PART_THREADS + tid];
+        for (uint32_t i = 0; KEYS ? __syncthreads_or(i < mine) != 0 : __ballot(i < mine) != 0ull; ++i) {
+            const bool has = i < mine;
+            uint32_t cb = 0, nk = 0;
+            if (has) {
+                cb = runb[i * PART_THREADS + tid];
                 const uint32_t bfld = 8u + 12u * i;
-                const uint32_t nk = (uint32_t)(bfld + 12 <= 64 ? sum_lo >> bfld : bfld >= 64 ? sum_hi >> (bfld - 64) : (sum_lo >> bfld) | (sum_hi << (64 - bfld))) & 63u;
-                if (lh) { const uint32_t bin = class_bin(cb, pp); atomicAdd(&lh[bin], 1u); atomicAdd(&lh[(PART_CLASSES << pp.log2_world) + bin], nk); }
-                else atomicAdd(&bucket_acc[cb], (1ull << 32) | nk);
+                nk = (uint32_t)(bfld + 12 <= 64 ? sum_lo >> bfld : bfld >= 64 ? sum_hi >> (bfld - 64) : (sum_lo >> bfld) | (sum_hi << (64 - bfld))) & 63u;
+                if constexpr (!KEYS) {
+                    if (lh) { const uint32_t bin = class_bin(cb, pp); atomicAdd(&lh[bin], 1u); atomicAdd(&lh[(PART_CLASSES << pp.log2_world) + bin], nk); }
+                    else atomicAdd(&bucket_acc[cb], (1ull << 32) | nk);
+                }
                 cmask |= 1u << sweep_class_of(cb & ((1u << log2_local) - 1u), log2_local);
+            }
+            if constexpr (KEYS) {
+                // a slot per key: one LDS add per wave for the stage, one per key for its class's count
+                const uint64_t m = __ballot(has);
+                if (m) {
+                    const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    const int lead = __ffsll((unsigned long long)m) - 1;
+                    uint32_t at = 0;
+                    if (has && rk == 0) at = atomicAdd(st_n, (uint32_t)__popcll(m));
+                    at = __shfl(at, lead) + rk;
+                    if (has) {
+                        const uint32_t cls = cb >> sk.ib;
+                        st_key[at] = ((cb & ((1u << sk.ib) - 1u)) << 6) | nk;
+                        st_cls[at] = (uint8_t)cls;
+                        atomicAdd(&st_h[cls], 1u);
+                    }
+                }
+                __syncthreads();
+                if (*st_n > (uint32_t)(SCAN_STAGE - PART_THREADS)) flush();
             }
         }
         if (r < n_reads) {
@@ -579,10 +649,99 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
             if (at < ovf_cap) ovf_list[at] = (uint32_t)r;
         }
     }
+    if constexpr (KEYS) { __syncthreads(); if (*st_n) flush(); }
     if (lh) {
         __syncthreads();
         for (uint32_t i = threadIdx.x; i < n_bins; i += PART_THREADS) if (lh[i]) atomicAdd(&class_hist[i], (unsigned long long)lh[i]);
     }
+}
+// LDS of the scan's staging, after its ring and run buckets
+constexpr size_t SCAN_STAGE_LDS = (sizeof(uint32_t) + 1) * SCAN_STAGE + (sizeof(unsigned long long) + sizeof(uint32_t)) * PART_CLASSES + sizeof(uint32_t);
+
+// per sub-slice (global number: bucket >> sb), the keys the class slices hold for it; grid (x, class)
+__global__ void __launch_bounds__(256)
+k_keys_subcount(const uint32_t* __restrict__ keys, const unsigned long long* __restrict__ fill, uint64_t cap, uint32_t sh /* 6 + sb */,
+                uint32_t n_sub, unsigned long long* __restrict__ sub_cnt)
+{
+    extern __shared__ uint32_t lh[];                                     // [n_sub]
+    const uint32_t c = blockIdx.y;
+    for (uint32_t i = threadIdx.x; i < n_sub; i += blockDim.x) lh[i] = 0;
+    __syncthreads();
+    const uint64_t n = min((uint64_t)fill[c], cap);
+    const uint32_t* k = keys + c * cap;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) atomicAdd(&lh[k[i] >> sh], 1u);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n_sub; i += blockDim.x) if (lh[i]) atomicAdd(&sub_cnt[(uint64_t)c * n_sub + i], (unsigned long long)lh[i]);
+}
+
+// exclusive prefix sums of the sub-slices' totals (one block): off[n + 1], and a copy in cur[n] for the partition's cursors
+__global__ void __launch_bounds__(1024)
+k_keys_offsets(const unsigned long long* __restrict__ cnt, uint32_t n, unsigned long long* __restrict__ off, unsigned long long* __restrict__ cur)
+{
+    __shared__ unsigned long long part[1024];
+    const uint32_t tid = threadIdx.x, per = (n + 1023) / 1024;
+    const uint32_t lo = min(n, tid * per), hi = min(n, lo + per);
+    unsigned long long s = 0;
+    for (uint32_t i = lo; i < hi; ++i) s += cnt[i];
+    part[tid] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const unsigned long long v = tid >= d ? part[tid - d] : 0ull;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    unsigned long long run = part[tid] - s;
+    for (uint32_t i = lo; i < hi; ++i) { off[i] = run; cur[i] = run; run += cnt[i]; }
+    if (tid == 1023) off[n] = part[1023];
+}
+
+// every class slice cut into its sub-slices: a block takes KEY_TILE keys at a time, counts them per sub-slice in LDS,
+// reserves room with one atomic per sub-slice present, and writes them there on a second read of the tile; grid (x, class)
+__global__ void __launch_bounds__(256)
+k_keys_partition(const uint32_t* __restrict__ keys, const unsigned long long* __restrict__ fill, uint64_t cap, uint32_t sh,
+                 uint32_t n_sub, unsigned long long* __restrict__ cur, uint32_t* __restrict__ out)
+{
+    extern __shared__ unsigned long long lds64[];
+    unsigned long long* base = lds64;                                    // [n_sub]
+    uint32_t* lh = reinterpret_cast<uint32_t*>(lds64 + n_sub);           // [n_sub]
+    const uint32_t c = blockIdx.y;
+    const uint64_t n = min((uint64_t)fill[c], cap);
+    const uint32_t* k = keys + c * cap;
+    unsigned long long* cc = cur + (uint64_t)c * n_sub;
+    for (uint64_t t0 = (uint64_t)blockIdx.x * KEY_TILE; t0 < n; t0 += (uint64_t)gridDim.x * KEY_TILE) {
+        const uint64_t t1 = min(n, t0 + KEY_TILE);
+        for (uint32_t i = threadIdx.x; i < n_sub; i += blockDim.x) lh[i] = 0;
+        __syncthreads();
+        for (uint64_t i = t0 + threadIdx.x; i < t1; i += blockDim.x) atomicAdd(&lh[k[i] >> sh], 1u);
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < n_sub; i += blockDim.x) { if (lh[i]) base[i] = atomicAdd(&cc[i], (unsigned long long)lh[i]); lh[i] = 0; }
+        __syncthreads();
+        for (uint64_t i = t0 + threadIdx.x; i < t1; i += blockDim.x) {
+            const uint32_t key = k[i], s = key >> sh;
+            out[base[s] + atomicAdd(&lh[s], 1u)] = key;
+        }
+        __syncthreads();
+    }
+}
+
+// a block per sub-slice: its 2^sb buckets' (1 << 32 | nk) sums in LDS, ADDED into bucket_acc (the scan's direct atomics and
+// the earlier pieces are already there)
+__global__ void __launch_bounds__(1024)
+k_keys_count(const uint32_t* __restrict__ part, const unsigned long long* __restrict__ off, uint32_t sb, unsigned long long* __restrict__ bucket_acc)
+{
+    __shared__ unsigned long long t[1u << KEY_SUB_BITS];
+    const uint32_t s = blockIdx.x, nt = 1u << sb, m = nt - 1u;
+    for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) t[i] = 0;
+    __syncthreads();
+    const uint64_t a = off[s], b = off[s + 1];
+    for (uint64_t i = a + threadIdx.x; i < b; i += blockDim.x) {
+        const uint32_t key = part[i];
+        atomicAdd(&t[(key >> 6) & m], (1ull << 32) | (key & 63u));
+    }
+    __syncthreads();
+    unsigned long long* dst = bucket_acc + ((uint64_t)s << sb);
+    for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) if (t[i]) dst[i] += t[i];
 }
 
 // Sharded scatter: the records of one pass go into one slice per owner rank, in no particular order inside

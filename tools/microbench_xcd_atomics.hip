@@ -38,6 +38,23 @@ __global__ void k_sum(const unsigned long long* tab, uint64_t words, int n_tabs,
     atomicAdd(total, acc);
 }
 
+// The same agent-scope atomics on smaller tables: is a window the size of one class of the scan's table (2^21 counters, 16 MB)
+// served faster than the whole 1-GB table?  (2 MB: inside one XCD's L2; 16 MB: the L2s together; 128 MB: inside the MALL)
+static void window_sizes(unsigned long long* tab, unsigned long long* ctr, hipEvent_t a, hipEvent_t b)
+{
+    const uint64_t n = 1ull << 32;
+    const uint64_t mb[4] = {2, 16, 128, 1024};
+    for (uint64_t m : mb) {
+        const uint64_t words = (m << 20) / 8;
+        CK(hipMemset(tab, 0, words * 8)); CK(hipMemset(ctr, 0, 64 * 8));
+        CK(hipEventRecord(a));
+        k<0><<<8192, 256>>>(tab, words, n, ctr);
+        CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
+        float ms; CK(hipEventElapsedTime(&ms, a, b));
+        printf("agent scope, one %5llu-MB table              %7.2f G atomics/s\n", (unsigned long long)m, n / ms / 1e6);
+    }
+}
+
 int main()
 {
     const uint64_t words = (1ull << 30) / 8, n = 1ull << 32;          // a 1 GB table, 4.3e9 operations
@@ -62,5 +79,6 @@ int main()
         for (int x = 0; x < 8; ++x) printf(" %llu", h[x]);
         printf("\n");
     }
+    window_sizes(tab, ctr, a, b);
     return 0;
 }
