@@ -506,7 +506,7 @@ int scan_keys_piece(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, ui
     auto* cur = off + n_subs + 1;
     HIP_TRY(hipMemsetAsync(J->fill.p, 0, J->n_cls * 8, c->stream));
     HIP_TRY(hipMemsetAsync(cnt, 0, n_subs * 8, c->stream));
-    const size_t lds = sizeof(uint32_t) * (PART_RING + SUMMARY_RUNS) * PART_THREADS + SCAN_STAGE_LDS;
+    const size_t lds = SCAN_RUN_LDS + SCAN_STAGE_LDS;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, true>), dim3(grid), dim3(PART_THREADS), lds, c->stream,
                        in.packed, in.packed_bytes, in.base_off, (const uint32_t*)c->good_len.p, r0, r1, J->pp,
                        (unsigned long long*)T->acc.p, (unsigned long long*)nullptr, (unsigned long long*)J->d_n.p, J->ovf_cap,
@@ -550,7 +550,7 @@ int scan_range(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, uint64_
             int rc = scan_keys_piece<K>(c, in, T, J, p0, std::min(r1, p0 + J->piece_reads)); if (rc) return rc;
         }
     } else if (scan_takes_ranges<K>(c)) {
-        const size_t lds_r = sizeof(uint32_t) * (PART_RING + SUMMARY_RUNS) * PART_THREADS + (by_class ? J->n_bins * 4 : 0);
+        const size_t lds_r = SCAN_RUN_LDS + (by_class ? J->n_bins * 4 : 0);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, false>), dim3(grid), dim3(PART_THREADS), lds_r, c->stream,
                            in.packed, in.packed_bytes, in.base_off, (const uint32_t*)c->good_len.p, r0, r1, pp,
                            (unsigned long long*)T->acc.p, (unsigned long long*)T->class_hist.p, (unsigned long long*)J->d_n.p, J->ovf_cap,

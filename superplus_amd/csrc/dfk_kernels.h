@@ -136,7 +136,7 @@ __host__ __device__ inline uint32_t sweep_class_mask(uint32_t sub_lo, uint32_t s
 }
 
 constexpr int PART_THREADS = 128;
-constexpr int PART_RING = 2;          // words of its read a lane of the counting scan keeps staged in LDS
+constexpr int PART_RING = 2;          // words of its read a lane of the general counting scan (k_partition) keeps staged in LDS
 // Per-read run summary written by the counting scan (16 bytes): bits 0-3 = number of runs (super-k-mers) or
 // SUMMARY_OVERFLOW, then from bit 8 twelve bits per run: nk (6) | offset of its minimizer from the run's
 // first k-mer (6, < W).  The scatter passes rebuild each run's bucket from the 2M bits at that offset
@@ -428,9 +428,13 @@ k_partition(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const uin
 // reads with too many runs -- with the block prefix / suffix minima of the sliding window kept in W + W registers per lane
 // instead of W x 5 bytes of LDS: the loop over a block of W m-mer positions is unrolled so that every index is a
 // compile-time constant.  What that buys: no LDS operation per base (there were six, with their address arithmetic), and
-// a run is closed by two register moves and an LDS store -- its bucket counter is bumped after the read's last base, in
+// a run is closed by register selects and LDS stores -- its bucket counter is bumped after the read's last base, in
 // a loop all lanes walk together -- where the per-base version paid the whole close (atomic, class mask, summary field)
 // as a divergent block in almost every step: among 64 reads some run ends nearly everywhere.
+// The bases come a block at a time: at the top of a block of W positions a lane issues the loads of the words that cover
+// the NEXT block (in flight while this one computes) and aligns the words it loaded a block earlier to its bit offset, so
+// that base bi of the block is a field at a constant place.  A run is closed with two LDS stores under exec (its bucket,
+// its 12-bit summary field); the summary's 64-bit fields and the class mask are built after the read, in the per-run loop.
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F&& f)
 {
@@ -451,7 +455,7 @@ struct ScanKeys {
     uint64_t cap;                     // room of a class slice
     uint32_t ib;                      // bits of a bucket within its class: log2_nb - min(6, log2_nb)
 };
-constexpr int SCAN_STAGE = 1792;      // keys a scan block stages (5 B each): with the scan's own 6 KB, 16 KB -- ten blocks a CU at K=40
+constexpr int SCAN_STAGE = 1536;      // keys a scan block stages (5 B each): with the scan's own 7.5 KB, under 16 KB -- ten blocks a CU at K=40
 constexpr uint32_t KEY_SUB_BITS = 14; // buckets of a sub-slice: 2^14 u64 counters = 128 KB of LDS
 constexpr uint32_t KEY_TILE = 16384;  // keys a partition block reserves room for at once (one atomic per sub-slice present)
 
@@ -469,18 +473,19 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
     constexpr int RUNS = SUMMARY_RUNS;                                   // buckets a lane remembers per read: as many as a summary holds
     static_assert(KTraits<K>::NK_MAX < 64, "nk takes the key's six low bits");
     extern __shared__ uint32_t smem[];
-    uint32_t* ring = smem;                                               // [PART_RING][PART_THREADS] words of the read
-    uint32_t* runb = smem + PART_RING * PART_THREADS;                    // [RUNS][PART_THREADS] bucket of each closed run
+    uint32_t* runb = smem;                                               // [RUNS][PART_THREADS] bucket of each closed run
+    uint16_t* runf = reinterpret_cast<uint16_t*>(runb + RUNS * PART_THREADS);   // [RUNS][PART_THREADS] its summary field: nk | rel << 6
+    uint32_t* const after_runs = reinterpret_cast<uint32_t*>(runf + RUNS * PART_THREADS);
     uint32_t* lh = nullptr;
     const uint32_t n_bins = 2u * (PART_CLASSES << pp.log2_world);
     if (class_hist) {
-        lh = runb + RUNS * PART_THREADS;
+        lh = after_runs;
         for (uint32_t i = threadIdx.x; i < n_bins; i += PART_THREADS) lh[i] = 0;
         __syncthreads();
     }
     const int tid = threadIdx.x;
     // KEYS: staged keys, their classes, per class the count staged and the room reserved for them in its slice
-    uint32_t* st_key = runb + RUNS * PART_THREADS;
+    uint32_t* st_key = after_runs;
     unsigned long long* st_base = reinterpret_cast<unsigned long long*>(st_key + SCAN_STAGE);
     uint32_t* st_h = reinterpret_cast<uint32_t*>(st_base + PART_CLASSES);
     uint32_t* st_n = st_h + PART_CLASSES;
@@ -517,25 +522,31 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
         uint64_t sum_lo = 0, sum_hi = 0;
         if (live) {
             const uint64_t bit0 = base_off[r] * 8;
-            uint64_t wi = bit0 >> 5, filled_to = wi;
-            auto fill = [&]() {
-                uint32_t w[PART_RING];
+            // words of the read: base j sits at bit bit0 + 2j, and bit0 is a byte boundary.  A block's W bases span 2W bits from
+            // an even offset, so NW words cover them and NA words hold them once aligned (K=40 / 48 / 60: NW 3 / 3 / 4, NA 2 / 3 / 3).
+            // Words past the end of packed read 0; the load itself is clamped so that no lane leaves the buffer.
+            constexpr int NW = (2 * W + 30 + 31) / 32, NA = (2 * W + 31) / 32;
+            auto load = [&](uint64_t bit, uint32_t (&w)[NW]) {
+                const uint64_t wi = bit >> 5;
 #pragma unroll
-                for (int k = 0; k < PART_RING; ++k) w[k] = filled_to + k < n_words ? words[filled_to + k] : 0u;
-#pragma unroll
-                for (int k = 0; k < PART_RING; ++k) ring[((filled_to + k) & (PART_RING - 1)) * PART_THREADS + tid] = w[k];
-                filled_to += PART_RING;
+                for (int k = 0; k < NW; ++k) {
+                    const uint64_t i = wi + k;
+                    const uint32_t v = words[i < n_words ? i : n_words - 1];
+                    w[k] = i < n_words ? v : 0u;
+                }
             };
-            fill();
-            uint32_t wbits = ring[(wi & (PART_RING - 1)) * PART_THREADS + tid], wpos = (uint32_t)bit0 & 31u;
-            auto next_base = [&]() -> uint32_t {
-                const uint32_t b = (wbits >> wpos) & 3u;
-                wpos += 2;
-                if (wpos == 32) { wpos = 0; ++wi; if (wi == filled_to) fill(); wbits = ring[(wi & (PART_RING - 1)) * PART_THREADS + tid]; }
-                return b;
-            };
+            uint64_t nbit = bit0 + 2 * (M - 1);                          // the first bit of the next block's bases
+            uint32_t nw[NW];
+            load(nbit, nw);                                              // block 0's words, in flight during the prologue
             uint32_t f = 0, rc = 0;
-            for (int j = 0; j < M - 1; ++j) { const uint32_t b = next_base(); f = ((f << 2) | b) & mmask; rc = (rc >> 2) | ((3u - b) << rsh); }
+            {
+                // the first M-1 bases: 2M-2 = 30 bits from a byte offset
+                const uint64_t wi = bit0 >> 5;
+                const uint32_t w0 = words[wi < n_words ? wi : n_words - 1], w1 = words[wi + 1 < n_words ? wi + 1 : n_words - 1];
+                const uint32_t pw = alignbit(wi + 1 < n_words ? w1 : 0u, wi < n_words ? w0 : 0u, (uint32_t)bit0 & 31u);
+#pragma unroll
+                for (int j = 0; j < M - 1; ++j) { const uint32_t b = (pw >> (2 * j)) & 3u; f = ((f << 2) | b) & mmask; rc = (rc >> 2) | ((3u - b) << rsh); }
+            }
             const uint32_t n_mmers = gl - M + 1;                         // m-mer positions t = 0 .. n_mmers-1; k-mer s = t-W+1 is complete at t >= W-1
             // suffix minima of the previous block, overwritten by the hashes of this one -- and where they sit, a BYTE each, four
             // to a register (every index is a constant once the block loop is unrolled: a field extract / insert).  With a word
@@ -551,9 +562,7 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
             auto close_run = [&]() {                                     // (cheap on purpose: see the head of this kernel)
                 if (qn < (uint32_t)RUNS) {
                     runb[qn * PART_THREADS + tid] = cur_b;
-                    const uint64_t fld = cur_nk | (cur_rel << 6);
-                    const uint32_t b = 8u + 12u * qn;
-                    if (b < 64u) { sum_lo |= fld << b; if (b > 52u) sum_hi |= fld >> (64u - b); } else sum_hi |= fld << (b - 64u);
+                    runf[qn * PART_THREADS + tid] = (uint16_t)(cur_nk | (cur_rel << 6));
                 } else {
                     // the eleventh run and beyond (two reads in 10^5 have them; the read then goes through the scanning scatter):
                     // counted on the spot
@@ -564,12 +573,21 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
                 ++qn;
             };
             for (uint32_t t0 = 0; t0 < n_mmers; t0 += W) {              // one block of W m-mer positions; t = t0 + bi
+                // this block's bases, aligned so that base bi is bits 2bi, 2bi+1 of the NA words; then the next block's loads
+                uint32_t a[NA];
+                {
+                    const uint32_t sh = (uint32_t)nbit & 31u;
+#pragma unroll
+                    for (int i = 0; i < NA; ++i) a[i] = alignbit(i + 1 < NW ? nw[i + 1] : 0u, nw[i], sh);
+                }
+                nbit += 2 * W;
+                load(nbit, nw);
                 // (expanded by template recursion, not `#pragma unroll`: at W = 45 the optimizer declines the pragma and arr[] goes
                 // to scratch; every index below must be a constant for arr[] / sidxw[] to be registers)
                 static_for<0, W>([&](auto bi_c) {
                     constexpr int bi = decltype(bi_c)::value;
                     if (t0 + (uint32_t)bi < n_mmers) {
-                        const uint32_t b = next_base();
+                        const uint32_t b = (a[(2 * bi) >> 5] >> ((2 * bi) & 31)) & 3u;
                         f = ((f << 2) | b) & mmask;
                         rc = (rc >> 2) | ((3u - b) << rsh);
                         const uint32_t h = mmer_hash(f < rc ? f : rc);
@@ -583,11 +601,11 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
                             if constexpr (bi != W - 1) { older = arr[bi + 1] < mv; mv = older ? arr[bi + 1] : mv; }
                             const uint32_t bucket = bucket_of(mv, pp);
                             const bool open = first || bucket != cur_b || cur_nk == (uint32_t)KTraits<K>::NK_MAX;
-                            if (open) {
-                                if (!first) close_run();
-                                cur_b = bucket; cur_nk = 1;
-                                cur_rel = (bi != W - 1 && older) ? sidx_get(bi + 1 < W ? bi + 1 : 0) - (uint32_t)bi - 1u : (uint32_t)(W - 1 - bi) + Pi;
-                            } else ++cur_nk;
+                            if (open && !first) close_run();
+                            const uint32_t rel = (bi != W - 1 && older) ? sidx_get(bi + 1 < W ? bi + 1 : 0) - (uint32_t)bi - 1u : (uint32_t)(W - 1 - bi) + Pi;
+                            cur_rel = open ? rel : cur_rel;
+                            cur_nk = open ? 1u : cur_nk + 1u;
+                            cur_b = open ? bucket : cur_b;
                         }
                         arr[bi] = h;
                         if (bi == W - 1) {                                // block complete: its hashes become suffix minima
@@ -611,8 +629,10 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
             uint32_t cb = 0, nk = 0;
             if (has) {
                 cb = runb[i * PART_THREADS + tid];
-                const uint32_t bfld = 8u + 12u * i;
-                nk = (uint32_t)(bfld + 12 <= 64 ? sum_lo >> bfld : bfld >= 64 ? sum_hi >> (bfld - 64) : (sum_lo >> bfld) | (sum_hi << (64 - bfld))) & 63u;
+                const uint64_t fld = runf[i * PART_THREADS + tid];
+                nk = (uint32_t)fld & 63u;
+                const uint32_t bfld = 8u + 12u * i;                      // (i is the same in every lane: these branches are uniform)
+                if (bfld < 64u) { sum_lo |= fld << bfld; if (bfld > 52u) sum_hi |= fld >> (64u - bfld); } else sum_hi |= fld << (bfld - 64u);
                 if constexpr (!KEYS) {
                     if (lh) { const uint32_t bin = class_bin(cb, pp); atomicAdd(&lh[bin], 1u); atomicAdd(&lh[(PART_CLASSES << pp.log2_world) + bin], nk); }
                     else atomicAdd(&bucket_acc[cb], (1ull << 32) | nk);
@@ -655,8 +675,10 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
         for (uint32_t i = threadIdx.x; i < n_bins; i += PART_THREADS) if (lh[i]) atomicAdd(&class_hist[i], (unsigned long long)lh[i]);
     }
 }
-// LDS of the scan's staging, after its ring and run buckets
+// LDS of the scan: its runs (bucket and summary field of each), then the class counts or (KEYS) the staging
+constexpr size_t SCAN_RUN_LDS = (sizeof(uint32_t) + sizeof(uint16_t)) * SUMMARY_RUNS * PART_THREADS;
 constexpr size_t SCAN_STAGE_LDS = (sizeof(uint32_t) + 1) * SCAN_STAGE + (sizeof(unsigned long long) + sizeof(uint32_t)) * PART_CLASSES + sizeof(uint32_t);
+static_assert(SCAN_RUN_LDS + SCAN_STAGE_LDS <= 16384, "ten scan blocks a CU (160 KB of LDS)");
 
 // per sub-slice (global number: bucket >> sb), the keys the class slices hold for it; grid (x, class)
 __global__ void __launch_bounds__(256)
