@@ -7,6 +7,7 @@ read set that is already resident in HBM when the timed region starts.
 
   python bench.py --gpus 1 --steps 3 --warmup 1
   python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs bench_outputs    (+ the last step's outputs, dump_outputs())
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full      (+ CPU baseline, parity check and the reported-only legs)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -22,9 +23,14 @@ RCCL all-to-all per pass, and a second small exchange settles cross-rank adjacen
 One JSON line on rank 0.  `roofline` is for the dominant kernel (k_count): algorithmic bytes
 = 64 B per k-mer instance (one 32-B sector read + one 32-B sector write of the
 owning table slot) divided by the kernel's duration from HIP events on the library's stream.
-`cpu_baseline` times the reference's own MapReduceEngine/KmerDict (oracle/_ref/refdrv, kind
-"reference") or, if that binary is absent, the C restatement (kind "port") on a bounded
-sample of the same workload on this host's cores.
+
+A plain run does only what that line needs: generate the set, warm up, time the steps (and
+--dump-outputs).  --full adds, after it, on one GPU: `cpu_baseline`, which times the reference's
+own MapReduceEngine/KmerDict (oracle/_ref/refdrv, kind "reference") or, if that binary is
+absent, the C restatement (kind "port") on a bounded sample of the same workload on this host's
+cores, with `parity_check` of the HIP path on that sample; and the reported-only legs of --legs
+(`extra`: K sweep, f-row and sharded rehearsals, repeat-rich genome, ParseBarcodedFastqs;
+`df_stage`: the DF stage's wall-clock).  --no-cpu-baseline / --no-extras drop either part.
 """
 import argparse
 import json
@@ -238,6 +244,23 @@ def solid_sample(entries, m, workers=16):
     return np.stack([w0l, w0h, w1l, w1h, kept["count_ctx"].astype(np.float64)], axis=1)
 
 
+def solid_entries(d, workers=16):
+    """d.solid_unsorted(), copied into pages that `workers` threads have faulted in first: at configs[1] (3.1e9 entries,
+    99 GB) the copy into untouched pages took 6.2 s, against 0.8 s of faulting by 16 threads and a 2.3 s copy."""
+    if not isinstance(d, Dfk):                                                     # (a stand-in context: tests)
+        return d.solid_unsorted()
+    import ctypes as C
+    from concurrent.futures import ThreadPoolExecutor
+    from superplus_amd.dfk import ENTRY_DTYPE, _check, _p, lib
+    n = d.solid_count()
+    out = np.empty(n, ENTRY_DTYPE)
+    base, size = out.ctypes.data, out.nbytes
+    with ThreadPoolExecutor(workers) as ex:                                        # (ctypes calls let go of the GIL)
+        list(ex.map(lambda a: C.memset(base + a, 0, min(1 << 30, size - a)), range(0, size, 1 << 30)))
+    _check(lib().dfk_solid_fetch_unsorted(d._ctx, _p(out), C.c_uint64(n), C.c_int(0)))
+    return out
+
+
 def dump_outputs(d, out_dir):
     """--dump-outputs: what the last timed step computed, as a caller of dfk_count_device receives it (rank 0's share in a
     multi-rank run), written as out_dir/<name>.npy in float64 so that two builds can be compared output for output:
@@ -256,7 +279,7 @@ def dump_outputs(d, out_dir):
               "spectrum": np.stack([nz.astype(np.float64), hist[nz].astype(np.float64)], axis=1)}
     lo, hi = u64_halves(d.digest())
     arrays["solid_digest"] = np.array([lo[0], hi[0], lo[1], hi[1]])
-    entries = d.solid_unsorted()
+    entries = solid_entries(d)
     arrays["solid_sample"] = solid_sample(entries, DUMP_SOLID_ROWS)
     del entries
     n = st["n_reads"]
@@ -552,11 +575,14 @@ def main():
     ap.add_argument("--K", type=int, default=48)
     ap.add_argument("--minimizer", type=int, default=0)
     ap.add_argument("--inst-per-item", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the CPU baseline with its parity check and the reported-only legs "
+                         "(one GPU only); a plain run measures the headline figure alone")
     ap.add_argument("--cpu-sample-reads", type=int, default=3000000,
                     help="reads of the sample the CPU baseline (and the parity check) runs on (about 30 s of reference code on 32 threads)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the reported-only legs (K sweep, repeat-rich genome, DF stage wall-clock)")
-    ap.add_argument("--legs", default="ksweep,repeat,rehearsal,pbf,df", help="which reported-only legs run (comma list of ksweep, repeat, rehearsal, pbf, df)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the reported-only legs (K sweep, repeat-rich genome, DF stage wall-clock)")
+    ap.add_argument("--legs", default="ksweep,repeat,rehearsal,pbf,df", help="with --full: which reported-only legs run (comma list of ksweep, repeat, rehearsal, pbf, df)")
     ap.add_argument("--pbf-pairs", type=int, default=2_000_000, help="pairs of the ParseBarcodedFastqs leg (configs[0] is ~5 M; 2 M keeps the default run short)")
     ap.add_argument("--extra-steps", type=int, default=3, help="timed steps of each reported-only leg")
     ap.add_argument("--family-copies", type=int, default=0,
@@ -745,7 +771,7 @@ def main():
         }
         if dist_timing is not None:
             out["dist_timing_ms"] = dist_timing
-        if world == 1 and not args.no_cpu_baseline and args.emulate_world <= 1:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.emulate_world <= 1:
             # The bounded sample: the workload at its own coverage over a proportionally smaller genome, so that the
             # reference's reduce sees the workload's k-mer multiplicities (the FIRST 6 M reads of the 1.8 G are 0.19x
             # of the genome: not one solid k-mer -- nothing to compare, and no dictionary for the CPU to build).
@@ -761,7 +787,7 @@ def main():
                 del rss
             except Exception as e:                       # the headline number must not depend on a reported-only leg
                 out["cpu_baseline_error"] = repr(e)
-        if world == 1 and not args.no_extras and args.emulate_world <= 1 and not multi:
+        if args.full and world == 1 and not args.no_extras and args.emulate_world <= 1 and not multi:
             extra = {}
             out["extra"] = extra
             # C5: the K sweep on the same reads

@@ -103,6 +103,11 @@ def test_dump_outputs_is_exact_bounded_and_independent_of_the_device_order(tmp_p
     assert np.array_equal(ctx.lens[idx], g[:, 1])
 
 
+def test_full_is_an_option():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "--full" in out.stdout
+
+
 def test_steps_below_one_are_refused():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
     assert out.returncode != 0 and "--steps" in out.stderr
@@ -128,3 +133,26 @@ def test_dumped_outputs_repeat_and_steps_are_the_timed_steps(tmp_path):
     assert runs[0].keys() == runs[1].keys()
     for k in runs[0]:
         assert np.array_equal(runs[0][k], runs[1][k]), k
+
+
+@pytest.mark.gpu
+def test_a_plain_run_is_the_headline_alone_and_full_adds_the_rest():
+    """Without --full the line carries the headline figure and what the timed steps report; --full adds the CPU baseline
+    with its parity check and the reported-only legs asked for."""
+    small = ["--gpus", "1", "--steps", "1", "--warmup", "0", "--genome-mb", "2", "--pairs", "200000"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--legs", "ksweep", "--extra-steps", "1", "--cpu-sample-reads", "20000"])):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *small, *extra], capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines[name] = json.loads(out.stdout.strip().splitlines()[-1])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["unit"] == "k-mers/s" and line["higher_is_better"] is True and line["dtype"] == "u64" and line["steps"] == 1
+        assert line["value"] > 0 and line["ms_per_step"] > 0
+    for k in ("n_reads", "n_inst", "n_records", "n_buckets", "n_distinct", "n_solid", "n_passes"):
+        assert plain["counts_rank0"][k] == full["counts_rank0"][k], k
+    assert not {"cpu_baseline", "cpu_baseline_error", "parity_check", "extra", "df_stage"} & plain.keys()
+    assert full["cpu_baseline"]["value"] > 0 and full["parity_check"]["status"] == "ok"
+    sweep = full["extra"]["k_sweep"]
+    assert sorted(sweep) == ["40", "48", "60"] and all("error" not in v for v in sweep.values())
+    assert "error" in full["df_stage"]                                             # (not among the legs asked for)

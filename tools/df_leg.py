@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the DF-stage leg of a bench.py JSON line (tools/df_leg.py gpurun_out/b.log)."""
+"""Print the DF-stage leg of a `bench.py --full` JSON line (tools/df_leg.py bench.log)."""
 import json, sys
 for l in open(sys.argv[1]):
     if not l.startswith('{'): continue
