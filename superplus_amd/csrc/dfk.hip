@@ -428,16 +428,27 @@ int table_totals(dfk_ctx* c, const DevBuf& acc, uint64_t nb, uint64_t* n_records
 // The counting scan in three steps, so that a caller whose reads are still arriving (count_host: the scan runs under the upload
 // of the bases) can run it a range of reads at a time: begin (tables, zeroed), range (a launch over reads [r0, r1)), end (the
 // overflow list, the totals, the check against the trim's instance count).  partition_count is all three over every read.
+constexpr uint64_t SCAN_TAIL_READS = 32ull << 20;   // the last piece of a keyed scan whose keys are counted under the next scan
 struct ScanJob {
     PartParams pp; uint64_t nb = 0, n_bins = 0, ovf_cap = 0; bool by_class = false, ranged = false;
     DevBuf ovf_tmp, d_n;
     // the register scan's run keys (k_scan_count<K, 16, true>): class slices, their partition into sub-slices, and per
     // sub-slice totals | offsets | cursors -- all scratch, counted a piece of at most piece_reads reads at a time
-    bool keyed = false; uint32_t n_cls = 0, n_sub = 0, sb = 0; uint64_t piece_reads = 0;
+    bool keyed = false; uint32_t n_cls = 0, n_sub = 0, sb = 0; uint64_t piece_reads = 0, tail_reads = 0;
     ScanKeys sk{};
     DevBuf keys, keys2, fill, sub;
+    // With a second stream the keys of piece i are counted under the scan of piece i + 1: `keys` and `fill` are n_slices = 2
+    // slices, piece i's scan (c->stream) fills slice i % 2, its subcount | offsets | partition follow on c->stream2, and its
+    // k_keys_count -- 128 KB of LDS, no room on a CU that holds scan blocks -- on c->stream behind the next scan.  The pipeline
+    // carries across scan_range calls (the pieces of run_under_upload); the range that ends the reads, and scan_end, drain it.
+    uint32_t n_slices = 1; uint64_t n_pieces = 0; bool count_due = false;
+    hipEvent_t ev_scan = nullptr, ev_count = nullptr, ev_part[2] = {nullptr, nullptr};   // last scan | last k_keys_count | last partition of a slice
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;                  // a pair per launch: ms_part_count is their sum
-    ~ScanJob() { for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } }
+    ~ScanJob()
+    {
+        for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+        for (hipEvent_t e : {ev_scan, ev_count, ev_part[0], ev_part[1]}) if (e) (void)hipEventDestroy(e);
+    }
 };
 
 // (the register scan takes ranges; the general scan -- other minimizer lengths -- only everything at once)
@@ -473,27 +484,49 @@ int scan_begin(dfk_ctx* c, const Inputs& in, uint32_t log2_world, int64_t read_i
         // a quarter to spare for reads longer than the mean and classes fuller than the mean (what still does not fit is
         // counted by the global atomic)
         const double per_read = 1.25 * runs;
-        // two copies of the keys (slices, partition); at most a third of what the arena can still give, and never more than
-        // KEY_SCRATCH_MAX, so that the pass plan after scan_end finds the arena as it was
+        // the keys' copies (a piece's slices, or two pieces' when they are counted under the next scan; their partition); at
+        // most a third of what the arena can still give, and never more than KEY_SCRATCH_MAX, so that the pass plan after
+        // scan_end finds the arena as it was
         constexpr uint64_t KEY_SCRATCH_MAX = 16ull << 30;
-        const uint64_t want = 8ull * (uint64_t)(per_read * (double)in.n_reads) + 8ull * J->n_cls;
+        J->n_slices = c->stream2 && !getenv("DFK_NO_OVERLAP") ? 2 : 1;
+        const uint32_t copies = J->n_slices + 1;
+        const uint64_t want = 4ull * copies * (uint64_t)(per_read * (double)in.n_reads) + 4ull * copies * J->n_cls;
         const uint64_t room = std::min<uint64_t>(std::min(want, KEY_SCRATCH_MAX), c->largest_allocatable() / 3);
-        J->sk.cap = std::max<uint64_t>(1024, room / 8 / J->n_cls);
+        J->sk.cap = std::max<uint64_t>(1024, room / (4 * copies) / J->n_cls) & ~3ull;   // (16-byte loads of the slices)
         J->piece_reads = std::max<uint64_t>(PART_THREADS, (uint64_t)((double)(J->sk.cap * J->n_cls) / per_read));
         if (const char* e = getenv("DFK_SCAN_KEY_PIECE")) J->piece_reads = std::max<uint64_t>(1, std::min<uint64_t>(J->piece_reads, strtoull(e, nullptr, 10)));
+        // the last piece's keys have no scan to be counted under: the pieces halve towards the end of the reads, down to
+        // tail_reads (profiles/r07_scan_overlap.txt: flat from 0 to 64 M reads; every extra piece is a k_keys_count launch)
+        J->tail_reads = getenv("DFK_SCAN_KEY_TAIL") ? strtoull(getenv("DFK_SCAN_KEY_TAIL"), nullptr, 10) : SCAN_TAIL_READS;
         const uint64_t n_subs = (uint64_t)J->n_cls * J->n_sub;
-        rc = c->alloc(J->keys, J->sk.cap * J->n_cls * 4, "run keys (scratch)"); if (rc) return rc;
+        rc = c->alloc(J->keys, J->n_slices * J->sk.cap * J->n_cls * 4, "run keys (scratch)"); if (rc) return rc;
         rc = c->alloc(J->keys2, J->sk.cap * J->n_cls * 4, "run keys by sub-slice (scratch)"); if (rc) return rc;
-        rc = c->alloc(J->fill, J->n_cls * 8, "run key slice fills (scratch)"); if (rc) return rc;
+        rc = c->alloc(J->fill, J->n_slices * J->n_cls * 8, "run key slice fills (scratch)"); if (rc) return rc;
         rc = c->alloc(J->sub, (3 * n_subs + 1) * 8, "run key sub-slices (scratch)"); if (rc) return rc;
-        J->sk.keys = (uint32_t*)J->keys.p; J->sk.fill = (unsigned long long*)J->fill.p;
-        TRACE("run keys: %u classes of %llu keys, %u sub-slices each, pieces of %llu reads", J->n_cls, (unsigned long long)J->sk.cap,
+        if (J->n_slices > 1)
+            for (hipEvent_t* e : {&J->ev_scan, &J->ev_count, &J->ev_part[0], &J->ev_part[1]}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        TRACE("run keys: %u x %u classes of %llu keys, %u sub-slices each, pieces of %llu reads", J->n_slices, J->n_cls, (unsigned long long)J->sk.cap,
               J->n_sub, (unsigned long long)J->piece_reads);
     }
     return 0;
 }
 
-// the counting scan over reads [r0, r1) with run keys, then the keys counted into bucket_acc
+// piece i's k_keys_count, queued on c->stream once its partition (c->stream2) is done
+inline int scan_keys_count(dfk_ctx* c, BucketTable* T, ScanJob* J)
+{
+    const uint64_t n_subs = (uint64_t)J->n_cls * J->n_sub;
+    const auto* off = (const unsigned long long*)J->sub.p + n_subs;
+    if (J->n_slices > 1) HIP_TRY(hipStreamWaitEvent(c->stream, J->ev_part[(J->n_pieces - 1) & 1], 0));
+    hipLaunchKernelGGL(k_keys_count, dim3((unsigned)n_subs), dim3(1024), 0, c->stream,
+                       (const uint32_t*)J->keys2.p, off, J->sb, (unsigned long long*)T->acc.p);
+    HIP_TRY(hipGetLastError());
+    if (J->n_slices > 1) HIP_TRY(hipEventRecord(J->ev_count, c->stream));
+    J->count_due = false;
+    return 0;
+}
+
+// the counting scan over reads [r0, r1) with run keys, then the keys counted into bucket_acc -- on one stream in that order,
+// or (two slices) the counting left to run under the next piece's scan: see ScanJob
 template <int K>
 int scan_keys_piece(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, uint64_t r0, uint64_t r1)
 {
@@ -501,31 +534,61 @@ int scan_keys_piece(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, ui
     const unsigned cus = (unsigned)c->prop.multiProcessorCount;
     const unsigned grid = (unsigned)std::min<uint64_t>((r1 - r0 + PART_THREADS - 1) / PART_THREADS, (uint64_t)(scan_blocks ? scan_blocks : 128u) * cus);
     const uint64_t n_subs = (uint64_t)J->n_cls * J->n_sub;
+    const bool two = J->n_slices > 1;
+    const uint32_t sl = two ? (uint32_t)(J->n_pieces & 1) : 0;
+    hipStream_t ks = two ? c->stream2 : c->stream;                       // subcount, offsets, partition
     auto* cnt = (unsigned long long*)J->sub.p;
     auto* off = cnt + n_subs;
     auto* cur = off + n_subs + 1;
-    HIP_TRY(hipMemsetAsync(J->fill.p, 0, J->n_cls * 8, c->stream));
-    HIP_TRY(hipMemsetAsync(cnt, 0, n_subs * 8, c->stream));
+    ScanKeys sk = J->sk;
+    sk.keys = (uint32_t*)J->keys.p + (uint64_t)sl * sk.cap * J->n_cls;
+    sk.fill = (unsigned long long*)J->fill.p + (uint64_t)sl * J->n_cls;
+    if (two && J->n_pieces >= 2) HIP_TRY(hipStreamWaitEvent(c->stream, J->ev_part[sl], 0));   // the slice's last reader
+    HIP_TRY(hipMemsetAsync(sk.fill, 0, J->n_cls * 8, c->stream));
     const size_t lds = SCAN_RUN_LDS + SCAN_STAGE_LDS;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, true>), dim3(grid), dim3(PART_THREADS), lds, c->stream,
                        in.packed, in.packed_bytes, in.base_off, (const uint32_t*)c->good_len.p, r0, r1, J->pp,
                        (unsigned long long*)T->acc.p, (unsigned long long*)nullptr, (unsigned long long*)J->d_n.p, J->ovf_cap,
-                       (uint32_t*)J->ovf_tmp.p, (uint4*)T->summ.p, (uint32_t*)T->classes.p, J->sk);
+                       (uint32_t*)J->ovf_tmp.p, (uint4*)T->summ.p, (uint32_t*)T->classes.p, sk);
     HIP_TRY(hipGetLastError());
+    if (two) {
+        HIP_TRY(hipEventRecord(J->ev_scan, c->stream));
+        // the piece before: its partition has had this scan to run under; its count frees keys2 and the sub-slice tables
+        if (J->count_due) { int rc = scan_keys_count(c, T, J); if (rc) return rc; }
+        HIP_TRY(hipStreamWaitEvent(ks, J->ev_scan, 0));
+        if (J->n_pieces >= 1) HIP_TRY(hipStreamWaitEvent(ks, J->ev_count, 0));
+    }
+    HIP_TRY(hipMemsetAsync(cnt, 0, n_subs * 8, ks));
     const dim3 per_class(std::max(1u, 16u * cus / J->n_cls), J->n_cls);
     const uint32_t sh = 6 + J->sb;
-    hipLaunchKernelGGL(k_keys_subcount, per_class, dim3(256), J->n_sub * 4, c->stream,
-                       (const uint32_t*)J->keys.p, (const unsigned long long*)J->fill.p, J->sk.cap, sh, J->n_sub, cnt);
+    hipLaunchKernelGGL(k_keys_subcount, per_class, dim3(256), J->n_sub * 4, ks,
+                       (const uint32_t*)sk.keys, (const unsigned long long*)sk.fill, sk.cap, sh, J->n_sub, cnt);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_keys_offsets, dim3(1), dim3(1024), 0, c->stream, (const unsigned long long*)cnt, (uint32_t)n_subs, off, cur);
+    hipLaunchKernelGGL(k_keys_offsets, dim3(1), dim3(1024), 0, ks, (const unsigned long long*)cnt, (uint32_t)n_subs, off, cur);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_keys_partition, per_class, dim3(256), J->n_sub * 12, c->stream,
-                       (const uint32_t*)J->keys.p, (const unsigned long long*)J->fill.p, J->sk.cap, sh, J->n_sub, cur, (uint32_t*)J->keys2.p);
+    hipLaunchKernelGGL(k_keys_partition, per_class, dim3(256), J->n_sub * 12, ks,
+                       (const uint32_t*)sk.keys, (const unsigned long long*)sk.fill, sk.cap, sh, J->n_sub, cur, (uint32_t*)J->keys2.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_keys_count, dim3((unsigned)n_subs), dim3(1024), 0, c->stream,
-                       (const uint32_t*)J->keys2.p, (const unsigned long long*)off, J->sb, (unsigned long long*)T->acc.p);
-    HIP_TRY(hipGetLastError());
+    if (two) HIP_TRY(hipEventRecord(J->ev_part[sl], ks));
+    ++J->n_pieces; J->count_due = true;
+    if (!two) return scan_keys_count(c, T, J);
     return 0;
+}
+
+// the pieces of reads [r0, r1): of piece_reads, and -- where the range ends the reads and the keys are counted under the
+// next scan -- halving over the last ones down to tail_reads, so that little is left to count when the last scan ends
+// (a piece's counting takes under half its scan's time)
+inline std::vector<uint64_t> scan_piece_sizes(const ScanJob* J, uint64_t n, bool last)
+{
+    std::vector<uint64_t> tail;
+    uint64_t t_sum = 0;
+    if (last && J->n_slices > 1 && J->tail_reads)
+        for (uint64_t t = J->tail_reads; t < J->piece_reads && t_sum + t < n; t *= 2) { tail.push_back(t); t_sum += t; }
+    std::vector<uint64_t> v;
+    const uint64_t body = n - t_sum, nb = (body + J->piece_reads - 1) / J->piece_reads;
+    for (uint64_t i = 0, at = 0; i < nb; ++i) { const uint64_t e = body * (i + 1) / nb; v.push_back(e - at); at = e; }
+    v.insert(v.end(), tail.rbegin(), tail.rend());
+    return v;
 }
 
 template <int K>
@@ -546,9 +609,13 @@ int scan_range(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, uint64_
     // the minimizer length everybody uses gets the scan whose window lives in registers (all three K since the positions are
     // packed four to a register); other lengths the general one
     if (J->keyed) {
-        for (uint64_t p0 = r0; p0 < r1; p0 += J->piece_reads) {
-            int rc = scan_keys_piece<K>(c, in, T, J, p0, std::min(r1, p0 + J->piece_reads)); if (rc) return rc;
+        uint64_t p0 = r0;
+        for (uint64_t m : scan_piece_sizes(J, r1 - r0, r1 == in.n_reads)) {
+            int rc = scan_keys_piece<K>(c, in, T, J, p0, p0 + m); if (rc) return rc;
+            p0 += m;
         }
+        // (ms_part_count runs until the bucket totals exist)
+        if (r1 == in.n_reads && J->count_due) { int rc = scan_keys_count(c, T, J); if (rc) return rc; }
     } else if (scan_takes_ranges<K>(c)) {
         const size_t lds_r = SCAN_RUN_LDS + (by_class ? J->n_bins * 4 : 0);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, false>), dim3(grid), dim3(PART_THREADS), lds_r, c->stream,
@@ -573,7 +640,8 @@ int scan_end(dfk_ctx* c, const Inputs& in, uint64_t n_inst, BucketTable* T, Scan
 {
     int rc = 0;
     T->n_ovf = 0;
-    c->release(J->keys); c->release(J->keys2); c->release(J->fill); c->release(J->sub);   // (stream-ordered: the counting is queued)
+    if (J->count_due) { rc = scan_keys_count(c, T, J); if (rc) return rc; }   // (a job whose ranges stopped short of the last read)
+    c->release(J->keys); c->release(J->keys2); c->release(J->fill); c->release(J->sub);   // (stream-ordered: the counting is queued on c->stream, behind the second stream's last kernel)
     if (in.n_reads) {
         HIP_TRY(hipMemcpyAsync(&T->n_ovf, J->d_n.p, 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));

@@ -457,7 +457,7 @@ struct ScanKeys {
 };
 constexpr int SCAN_STAGE = 1536;      // keys a scan block stages (5 B each): with the scan's own 7.5 KB, under 16 KB -- ten blocks a CU at K=40
 constexpr uint32_t KEY_SUB_BITS = 14; // buckets of a sub-slice: 2^14 u64 counters = 128 KB of LDS
-constexpr uint32_t KEY_TILE = 16384;  // keys a partition block reserves room for at once (one atomic per sub-slice present)
+constexpr uint32_t KEY_TILE = 4096;   // keys a partition block holds in registers and reserves room for at once (one atomic per sub-slice present)
 
 template <int K, int M, bool KEYS>
 __global__ void __launch_bounds__(PART_THREADS)
@@ -680,6 +680,39 @@ constexpr size_t SCAN_RUN_LDS = (sizeof(uint32_t) + sizeof(uint16_t)) * SUMMARY_
 constexpr size_t SCAN_STAGE_LDS = (sizeof(uint32_t) + 1) * SCAN_STAGE + (sizeof(unsigned long long) + sizeof(uint32_t)) * PART_CLASSES + sizeof(uint32_t);
 static_assert(SCAN_RUN_LDS + SCAN_STAGE_LDS <= 16384, "ten scan blocks a CU (160 KB of LDS)");
 
+// The three kernels below run on the second stream beside the NEXT piece's scan, in what its waves leave of a SIMD (64 VGPRs
+// at K=48, 32 at K=40), so a wave is at most 32 VGPRs and keeps KEY_VECS 16-byte loads in flight.  A thread's j-th vector
+// of a tile holds keys [(j * 256 + tid) * 4, +4); key_tile_load leaves vectors past the end zero, key_vec_n says how many
+// of a vector's keys count (slices are 16-byte aligned and a multiple of 4 keys long: a vector never leaves its slice).
+constexpr int KEY_VECS = 4;
+static_assert(KEY_TILE == 256u * 4u * KEY_VECS, "a tile is KEY_VECS 16-byte vectors per thread of a 256-thread block");
+__device__ __forceinline__ uint32_t key_vec_n(uint64_t t0, uint64_t t1, int j)
+{
+    const uint64_t i = t0 + ((uint64_t)j * 256u + threadIdx.x) * 4u;
+    return i < t1 ? (uint32_t)min((uint64_t)4, t1 - i) : 0u;
+}
+__device__ __forceinline__ void key_tile_load(const uint32_t* __restrict__ k, uint64_t t0, uint64_t t1, uint4 (&v)[KEY_VECS])
+{
+#pragma unroll
+    for (int j = 0; j < KEY_VECS; ++j) {
+        const uint64_t i = t0 + ((uint64_t)j * 256u + threadIdx.x) * 4u;
+        v[j] = i < t1 ? *reinterpret_cast<const uint4*>(k + i) : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+template <typename F>
+__device__ __forceinline__ void key_tile_each(uint64_t t0, uint64_t t1, const uint4 (&v)[KEY_VECS], F&& f)
+{
+#pragma unroll
+    for (int j = 0; j < KEY_VECS; ++j) {
+        const uint32_t m = key_vec_n(t0, t1, j);
+        if (m > 0) f(v[j].x);
+        if (m > 1) f(v[j].y);
+        if (m > 2) f(v[j].z);
+        if (m > 3) f(v[j].w);
+        __builtin_amdgcn_sched_barrier(0);                               // (a vector at a time: not a tile's sixteen store addresses live at once)
+    }
+}
+
 // per sub-slice (global number: bucket >> sb), the keys the class slices hold for it; grid (x, class)
 __global__ void __launch_bounds__(256)
 k_keys_subcount(const uint32_t* __restrict__ keys, const unsigned long long* __restrict__ fill, uint64_t cap, uint32_t sh /* 6 + sb */,
@@ -691,7 +724,12 @@ k_keys_subcount(const uint32_t* __restrict__ keys, const unsigned long long* __r
     __syncthreads();
     const uint64_t n = min((uint64_t)fill[c], cap);
     const uint32_t* k = keys + c * cap;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) atomicAdd(&lh[k[i] >> sh], 1u);
+    for (uint64_t t0 = (uint64_t)blockIdx.x * KEY_TILE; t0 < n; t0 += (uint64_t)gridDim.x * KEY_TILE) {
+        const uint64_t t1 = min(n, t0 + KEY_TILE);
+        uint4 v[KEY_VECS];
+        key_tile_load(k, t0, t1, v);
+        key_tile_each(t0, t1, v, [&](uint32_t key) { atomicAdd(&lh[key >> sh], 1u); });
+    }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < n_sub; i += blockDim.x) if (lh[i]) atomicAdd(&sub_cnt[(uint64_t)c * n_sub + i], (unsigned long long)lh[i]);
 }
@@ -718,8 +756,8 @@ k_keys_offsets(const unsigned long long* __restrict__ cnt, uint32_t n, unsigned 
     if (tid == 1023) off[n] = part[1023];
 }
 
-// every class slice cut into its sub-slices: a block takes KEY_TILE keys at a time, counts them per sub-slice in LDS,
-// reserves room with one atomic per sub-slice present, and writes them there on a second read of the tile; grid (x, class)
+// every class slice cut into its sub-slices: a block takes KEY_TILE keys at a time into registers, counts them per sub-slice
+// in LDS, reserves room with one atomic per sub-slice present, and writes them there from the registers; grid (x, class)
 __global__ void __launch_bounds__(256)
 k_keys_partition(const uint32_t* __restrict__ keys, const unsigned long long* __restrict__ fill, uint64_t cap, uint32_t sh,
                  uint32_t n_sub, unsigned long long* __restrict__ cur, uint32_t* __restrict__ out)
@@ -733,22 +771,24 @@ k_keys_partition(const uint32_t* __restrict__ keys, const unsigned long long* __
     unsigned long long* cc = cur + (uint64_t)c * n_sub;
     for (uint64_t t0 = (uint64_t)blockIdx.x * KEY_TILE; t0 < n; t0 += (uint64_t)gridDim.x * KEY_TILE) {
         const uint64_t t1 = min(n, t0 + KEY_TILE);
+        uint4 v[KEY_VECS];
+        key_tile_load(k, t0, t1, v);
         for (uint32_t i = threadIdx.x; i < n_sub; i += blockDim.x) lh[i] = 0;
         __syncthreads();
-        for (uint64_t i = t0 + threadIdx.x; i < t1; i += blockDim.x) atomicAdd(&lh[k[i] >> sh], 1u);
+        key_tile_each(t0, t1, v, [&](uint32_t key) { atomicAdd(&lh[key >> sh], 1u); });
         __syncthreads();
         for (uint32_t i = threadIdx.x; i < n_sub; i += blockDim.x) { if (lh[i]) base[i] = atomicAdd(&cc[i], (unsigned long long)lh[i]); lh[i] = 0; }
         __syncthreads();
-        for (uint64_t i = t0 + threadIdx.x; i < t1; i += blockDim.x) {
-            const uint32_t key = k[i], s = key >> sh;
-            out[base[s] + atomicAdd(&lh[s], 1u)] = key;
-        }
+        uint32_t sh2 = sh;
+        asm volatile("" : "+s"(sh2));                                    // (the sub-slices are worked out again: kept from the count, they and their LDS addresses are 32 VGPRs)
+        key_tile_each(t0, t1, v, [&](uint32_t key) { const uint32_t s = key >> sh2; out[base[s] + atomicAdd(&lh[s], 1u)] = key; });
         __syncthreads();
     }
 }
 
-// a block per sub-slice: its 2^sb buckets' (1 << 32 | nk) sums in LDS, ADDED into bucket_acc (the scan's direct atomics and
-// the earlier pieces are already there)
+// a block per sub-slice: its 2^sb buckets' (1 << 32 | nk) sums in LDS, ADDED into bucket_acc.  The add is an atomic (without
+// return, one per bucket the piece touched): the next piece's scan is running and adds to the same table with its direct
+// atomics (runs beyond a summary, keys that found their class slice full), which a load and a store would lose.
 __global__ void __launch_bounds__(1024)
 k_keys_count(const uint32_t* __restrict__ part, const unsigned long long* __restrict__ off, uint32_t sb, unsigned long long* __restrict__ bucket_acc)
 {
@@ -763,7 +803,7 @@ k_keys_count(const uint32_t* __restrict__ part, const unsigned long long* __rest
     }
     __syncthreads();
     unsigned long long* dst = bucket_acc + ((uint64_t)s << sb);
-    for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) if (t[i]) dst[i] += t[i];
+    for (uint32_t i = threadIdx.x; i < nt; i += blockDim.x) if (t[i]) atomicAdd(&dst[i], t[i]);
 }
 
 // Sharded scatter: the records of one pass go into one slice per owner rank, in no particular order inside
