@@ -687,8 +687,8 @@ int main(int argc, char** argv)
             h_packed = x.fb.m.p; h_boff = x.fb.off_table(); h_len = x.fb.fixed();
             h_pq = x.qp.m.p; h_qoff = x.qp.off_table();
             const bool may_link = truthy(a["LINK_READS"]);
-            if (!(may_link && link_feudal(x.fb, rh + ".fastb", 4, 16, 1))) in_background([&] { copy_feudal(x.fb, rh + ".fastb", 4, 16, 1); });      // (two files, two writers)
-            if (!(may_link && link_feudal(x.qp, rh + ".qualp", 0, 8, 1))) in_background([&] { copy_feudal(x.qp, rh + ".qualp", 0, 8, 1); });
+            if (!(may_link && link_feudal(x.fb, rh + ".fastb", 4, 16, 1))) in_background([&x, rh] { copy_feudal(x.fb, rh + ".fastb", 4, 16, 1); });      // (two files, two writers; rh by value: a refused table unwinds this scope before the writers are joined)
+            if (!(may_link && link_feudal(x.qp, rh + ".qualp", 0, 8, 1))) in_background([&x, rh] { copy_feudal(x.qp, rh + ".qualp", 0, 8, 1); });
             in_background([&bci, rh] { feudal::BinWriter w(rh + ".bci"); w.vec(bci); });     // (the count thread, which reads bci too, is not kept waiting for it)
         } else {
             R.base_off.push_back(0); R.pq_off.push_back(0);

@@ -2,6 +2,7 @@
 // HIP kernels in dfk_kernels.h.  gfx950 only; there is no CPU path in this library.
 #include "../../include/dfk.h"
 #include "dfk_kernels.h"
+#include "dfk_arena.h"
 
 #include <algorithm>
 #include <chrono>
@@ -49,10 +50,17 @@ template <class F> int guarded(F&& f)
     catch (...) { return fail(DFK_E_HIP, "internal error"); }
 }
 
-struct DevBuf {
-    void* p = nullptr; size_t bytes = 0;
-    bool sub = false;            // carved from a pass block (dfk_ctx::PassBlock): given back with the block, not on its own
-};
+// the arena's backing store: chunks straight from the driver
+void* dev_get(uint64_t bytes, const char** why)
+{
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) return p;
+    (void)hipGetLastError();                          // (a failed attempt is not an error of the next launch)
+    *why = hipGetErrorString(e);
+    return nullptr;
+}
+void dev_give(void* p) { (void)hipFree(p); }
 
 bool g_trace = getenv("DFK_TRACE") != nullptr;
 #define TRACE(...) do { if (g_trace) { fprintf(stderr, "[dfk] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
@@ -85,10 +93,15 @@ struct dfk_ctx {
     hipStream_t stream = nullptr;             // everything except ...
     hipStream_t stream2 = nullptr;            // ... the scatter of the next pass, which runs (low priority) under the count of the current one
     hipDeviceProp_t prop{};
-    uint64_t budget = 0, held = 0, peak = 0;
-    struct Owned { void* p; uint64_t bytes, seq; };
-    std::vector<Owned> owned;                 // live blocks of the arena, in allocation order
-    uint64_t alloc_seq = 0;
+    dfk::Arena arena{dev_get, dev_give};       // all device memory of a run (dfk_arena.h); the members below forward to it
+    uint64_t &budget = arena.budget, &held = arena.held, &peak = arena.peak, &alloc_seq = arena.alloc_seq, &first_chunk_hint = arena.first_chunk_hint;
+    int alloc(DevBuf& b, size_t bytes, const char* what, Place where = Place::High) { return arena.alloc(b, bytes, what, where) ? fail(DFK_E_NOMEM, "%s", arena.err.c_str()) : 0; }
+    void release(DevBuf& b) { arena.release(b); }
+    void shrink(DevBuf& b, size_t keep) { arena.shrink(b, keep); }
+    void release_since(uint64_t mark, const DevBuf* keep = nullptr) { arena.release_since(mark, keep); }
+    uint64_t largest_allocatable() const { return arena.largest_allocatable(); }
+    void drop_empty_chunks() { arena.drop_empty_chunks(); }
+    void drop_pool() { arena.drop_pool(); }
     // results of the last run
     bool have = false;
     uint64_t n_reads = 0;
@@ -142,138 +155,6 @@ struct dfk_ctx {
     void* kept[6] = {};
     uint64_t kept_packed_bytes = 0, kept_pq_bytes = 0, kept_n_reads = 0, kept_budget = 0;
 
-    // Device memory comes from a few large chunks that are kept for the life of the context and managed
-    // by first-fit free lists with coalescing.  hipMalloc/hipFree of multi-GB blocks cost milliseconds to
-    // seconds each (and hipFree synchronises the device); a 30x human run moves hundreds of GB per pass.
-    struct Free { uint64_t off, bytes; };
-    struct Chunk { char* p; uint64_t bytes; std::vector<Free> free_list; bool adopted = false; };     // free_list sorted by offset; adopted: see adopt_kept
-    std::vector<Chunk> chunks;
-    uint64_t reserved = 0;                           // sum of chunk sizes
-
-    uint64_t first_chunk_hint = 0;                   // set from the input size before a run: one big chunk, no growth
-    // long-lived blocks (dictionary parts, goodLens, bucket counters, summaries) grow from the bottom of the chunk,
-    // per-pass blocks and temporaries come from the top, so that the two kinds do not fragment each other
-    bool carve(Chunk& k, size_t bytes, DevBuf& b, bool long_lived)
-    {
-        if (!long_lived) {                              // temporaries: the highest free block that fits, its upper end
-            for (size_t i = k.free_list.size(); i-- > 0;)
-                if (k.free_list[i].bytes >= bytes) {
-                    k.free_list[i].bytes -= bytes;
-                    b.p = k.p + k.free_list[i].off + k.free_list[i].bytes; b.bytes = bytes;
-                    if (!k.free_list[i].bytes) k.free_list.erase(k.free_list.begin() + i);
-                    return true;
-                }
-            return false;
-        }
-        for (size_t i = 0; i < k.free_list.size(); ++i)  // long-lived: the lowest free block that fits, its lower end
-            if (k.free_list[i].bytes >= bytes) {
-                b.p = k.p + k.free_list[i].off; b.bytes = bytes;
-                k.free_list[i].off += bytes; k.free_list[i].bytes -= bytes;
-                if (!k.free_list[i].bytes) k.free_list.erase(k.free_list.begin() + i);
-                return true;
-            }
-        return false;
-    }
-    void drop_empty_chunks()
-    {
-        for (size_t i = 0; i < chunks.size();)
-            if (chunks[i].free_list.size() == 1 && chunks[i].free_list[0].bytes == chunks[i].bytes)
-            { (void)hipFree(chunks[i].p); reserved -= chunks[i].bytes; chunks.erase(chunks.begin() + i); }
-            else ++i;
-    }
-    // Everything one pass holds while it is in flight (bucket tables, records) comes out of ONE
-    // arena block, so that two passes in flight plus the growing dictionary never interleave: the blocks of
-    // successive passes do not grow, so each fits the hole left by the pass before the running one.
-    struct PassBlock { DevBuf block; size_t used = 0; };
-    PassBlock* sub = nullptr;                        // while set, bottom allocations are bumped out of it when they fit
-    int alloc(DevBuf& b, size_t bytes, const char* what, bool top = false)
-    {
-        bytes = bytes ? (bytes + 255) & ~(size_t)255 : 256;
-        if (sub && !top && sub->used + bytes <= sub->block.bytes) {
-            b.p = (char*)sub->block.p + sub->used; b.bytes = bytes; b.sub = true;
-            sub->used += bytes;
-            return 0;
-        }
-        if (held + bytes > budget)
-            return fail(DFK_E_NOMEM, "HBM budget exceeded allocating %zu bytes for %s (held %llu, budget %llu)",
-                        bytes, what, (unsigned long long)held, (unsigned long long)budget);
-        bool ok = false;
-        for (Chunk& k : chunks) if (carve(k, bytes, b, top)) { ok = true; break; }
-        if (!ok) {
-            // grow: the first chunk is sized from the input (a run needs a few times its input), later ones
-            // twice the request (later requests reuse the slack); never past the budget
-            uint64_t want = std::max<uint64_t>(2 * (uint64_t)bytes, 64ull << 20);
-            if (chunks.empty()) want = std::max<uint64_t>(want, std::min<uint64_t>(first_chunk_hint, budget));
-            if (reserved + want > budget) { drop_empty_chunks(); want = std::min<uint64_t>(want, budget > reserved ? budget - reserved : 0); }
-            want &= ~(uint64_t)0xFFF;                  // blocks carved from the top of a chunk must stay aligned
-            if (want < bytes) {
-                if (g_trace) {
-                    for (const Chunk& k : chunks) for (const Free& f : k.free_list) fprintf(stderr, "[dfk]   free %.2f GB at %.2f GB\n", f.bytes / 1e9, f.off / 1e9);
-                    for (const Owned& o : owned) if (o.bytes >= (1ull << 28)) fprintf(stderr, "[dfk]   held %.2f GB at %.2f GB (#%llu)\n", o.bytes / 1e9, ((char*)o.p - chunks[0].p) / 1e9, (unsigned long long)o.seq);
-                }
-                return fail(DFK_E_NOMEM, "HBM budget exhausted by fragmentation allocating %zu bytes for %s", bytes, what);
-            }
-            void* p = nullptr;
-            hipError_t e = hipMalloc(&p, want);
-            if (e != hipSuccess && want > bytes) { (void)hipGetLastError(); want = bytes; e = hipMalloc(&p, want); }
-            if (e != hipSuccess) return fail(DFK_E_NOMEM, "hipMalloc(%llu) for %s: %s", (unsigned long long)want, what, hipGetErrorString(e));
-            chunks.push_back(Chunk{(char*)p, want, {Free{0, want}}});
-            reserved += want;
-            TRACE("new device chunk %p, %.2f GB (reserved %.2f of %.2f GB)", p, want / 1e9, (reserved) / 1e9, budget / 1e9);
-            carve(chunks.back(), bytes, b, top);
-        }
-        held += bytes; peak = std::max(peak, held);
-        owned.push_back(Owned{b.p, (uint64_t)bytes, ++alloc_seq});
-        if (bytes >= (1ull << 30)) TRACE("alloc %-28s %8.2f GB at %p (%s), held %.2f GB", what, bytes / 1e9, b.p, top ? "top" : "bottom", held / 1e9);
-        return 0;
-    }
-    // the largest block alloc() could hand out now: a free block of a chunk, or a new chunk within the budget
-    uint64_t largest_allocatable() const
-    {
-        uint64_t best = budget > reserved ? (budget - reserved) & ~(uint64_t)0xFFF : 0;
-        for (const Chunk& k : chunks) for (const Free& f : k.free_list) best = std::max<uint64_t>(best, f.bytes);
-        return std::min<uint64_t>(best, budget > held ? budget - held : 0);
-    }
-    void release(DevBuf& b)
-    {
-        if (!b.p) return;
-        if (b.sub) { b = DevBuf{}; return; }
-        auto it = std::find_if(owned.begin(), owned.end(), [&](const Owned& o) { return o.p == b.p; });
-        if (it != owned.end()) owned.erase(it);
-        for (Chunk& k : chunks)
-            if ((char*)b.p >= k.p && (char*)b.p < k.p + k.bytes) {
-                std::vector<Free>& fl = k.free_list;
-                const uint64_t off = (uint64_t)((char*)b.p - k.p);
-                size_t i = 0;
-                while (i < fl.size() && fl[i].off < off) ++i;
-                fl.insert(fl.begin() + i, Free{off, b.bytes});
-                if (i + 1 < fl.size() && fl[i].off + fl[i].bytes == fl[i + 1].off) { fl[i].bytes += fl[i + 1].bytes; fl.erase(fl.begin() + i + 1); }
-                if (i > 0 && fl[i - 1].off + fl[i - 1].bytes == fl[i].off) { fl[i - 1].bytes += fl[i].bytes; fl.erase(fl.begin() + i); }
-                break;
-            }
-        held -= b.bytes; b.p = nullptr; b.bytes = 0;
-    }
-    // keep only the first `keep` bytes of a block: a reservation made for an upper bound is cut to what was
-    // needed; the tail goes back to the free room above it (long-lived blocks grow upwards)
-    void shrink(DevBuf& b, size_t keep)
-    {
-        keep = keep ? (keep + 255) & ~(size_t)255 : 256;
-        if (!b.p || keep >= b.bytes) return;
-        auto it = std::find_if(owned.begin(), owned.end(), [&](const Owned& o) { return o.p == b.p; });
-        DevBuf tail; tail.p = (char*)b.p + keep; tail.bytes = b.bytes - keep;
-        b.bytes = keep;
-        if (it != owned.end()) { it->bytes = keep; owned.push_back(Owned{tail.p, (uint64_t)tail.bytes, it->seq}); }
-        else owned.push_back(Owned{tail.p, (uint64_t)tail.bytes, alloc_seq});
-        release(tail);
-    }
-    // give back everything allocated after `mark` (= alloc_seq at some earlier moment): what an abandoned
-    // pass left behind.  The DevBufs that pointed at those blocks are dead; the caller resets them.
-    void release_since(uint64_t mark)
-    {
-        for (size_t i = owned.size(); i-- > 0;)
-            if (owned[i].seq > mark) { DevBuf b; b.p = owned[i].p; b.bytes = owned[i].bytes; release(b); }
-    }
-    void drop_pool() { for (Chunk& k : chunks) (void)hipFree(k.p); chunks.clear(); reserved = 0; }
     void release_all()
     {
         // (an aborted sharded run may have left a partition registered for launch, or running on the second stream)
@@ -284,11 +165,7 @@ struct dfk_ctx {
         for (DevBuf* d : live) release(*d);
         for (Part& pt : parts) { release(pt.buf); release(pt.pre); }
         parts.clear();
-        // anything an aborted run left behind: the arena is simply declared empty again
-        owned.clear(); held = 0;
-        for (size_t i = 0; i < chunks.size();)                                // (what adopt_kept brought in goes back to the driver: a run plans with ONE large chunk)
-            if (chunks[i].adopted) { (void)hipFree(chunks[i].p); reserved -= chunks[i].bytes; chunks.erase(chunks.begin() + i); } else ++i;
-        for (Chunk& k : chunks) k.free_list.assign(1, Free{0, k.bytes});
+        arena.reset();                                                        // anything an aborted run left behind: the arena is simply declared empty again
         good_len = shard_send[0] = shard_send[1] = shard_recv[0] = shard_recv[1] = adj_keys = adj_src = set = DevBuf{};
         shard_send_pass[0] = shard_send_pass[1] = ~0u;
         have = false; sorted_ok = sorted_pre_ok = false; sorted.clear(); sorted_pre.clear(); hist.clear();
@@ -312,7 +189,7 @@ struct dfk_ctx {
         for (int i = 0; i < 6; ++i) {
             if (!kept[i]) continue;
             const uint64_t b = bytes[i] & ~(uint64_t)0xFFF;
-            if (i < 5 && b >= (64ull << 20) && ((uintptr_t)kept[i] & 0xFFF) == 0) { chunks.push_back(Chunk{(char*)kept[i], b, {Free{0, b}}, true}); reserved += b; }
+            if (i < 5 && b >= (64ull << 20) && ((uintptr_t)kept[i] & 0xFFF) == 0) arena.adopt(kept[i], b);
             else (void)hipFree(kept[i]);
             kept[i] = nullptr;
         }
@@ -338,7 +215,7 @@ int stage_trim(dfk_ctx* c, const Inputs& in, uint64_t* n_inst)
 {
     DevBuf ctr; int rc = c->alloc(ctr, 32, "trim counters"); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(ctr.p, 0, 32, c->stream));
-    rc = c->alloc(c->good_len, sizeof(uint32_t) * in.n_reads, "goodLens", true); if (rc) return rc;
+    rc = c->alloc(c->good_len, sizeof(uint32_t) * in.n_reads, "goodLens", Place::Low); if (rc) return rc;
     if (in.n_reads) {
         unsigned grid = (unsigned)std::min<uint64_t>((in.n_reads + 255) / 256, 8192);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trim<K>), dim3(grid), dim3(256), 0, c->stream,
@@ -461,10 +338,10 @@ int scan_begin(dfk_ctx* c, const Inputs& in, uint32_t log2_world, int64_t read_i
     J->nb = 1ull << T->log2_nb; J->by_class = by_class;
     int rc = 0;
     J->n_bins = 2ull * (PART_CLASSES << log2_world);
-    if (by_class) { rc = c->alloc(T->class_hist, J->n_bins * 8, "class counters", true); if (rc) return rc; HIP_TRY(hipMemsetAsync(T->class_hist.p, 0, J->n_bins * 8, c->stream)); }
-    else { rc = c->alloc(T->acc, J->nb * 8, "bucket counters", true); if (rc) return rc; }
-    rc = c->alloc(T->summ, std::max<uint64_t>(1, in.n_reads) * 16, "run summaries", true); if (rc) return rc;
-    rc = c->alloc(T->classes, std::max<uint64_t>(1, in.n_reads) * 4, "read bucket classes", true); if (rc) return rc;
+    if (by_class) { rc = c->alloc(T->class_hist, J->n_bins * 8, "class counters", Place::Low); if (rc) return rc; HIP_TRY(hipMemsetAsync(T->class_hist.p, 0, J->n_bins * 8, c->stream)); }
+    else { rc = c->alloc(T->acc, J->nb * 8, "bucket counters", Place::Low); if (rc) return rc; }
+    rc = c->alloc(T->summ, std::max<uint64_t>(1, in.n_reads) * 16, "run summaries", Place::Low); if (rc) return rc;
+    rc = c->alloc(T->classes, std::max<uint64_t>(1, in.n_reads) * 4, "read bucket classes", Place::Low); if (rc) return rc;
     if (!by_class) HIP_TRY(hipMemsetAsync(T->acc.p, 0, J->nb * 8, c->stream));
     // reads whose runs do not fit a summary are listed by the scan itself (two in 10^5 at 2x100 bp); if the list
     // outgrows the room set aside for it the summaries are searched instead
@@ -656,7 +533,7 @@ int scan_end(dfk_ctx* c, const Inputs& in, uint64_t n_inst, BucketTable* T, Scan
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
         if (T->n_ovf) {
-            rc = c->alloc(T->ovf_list, T->n_ovf * 4, "overflow read list", true); if (rc) return rc;
+            rc = c->alloc(T->ovf_list, T->n_ovf * 4, "overflow read list", Place::Low); if (rc) return rc;
             HIP_TRY(hipMemcpyAsync(T->ovf_list.p, J->ovf_tmp.p, T->n_ovf * 4, hipMemcpyDeviceToDevice, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
@@ -842,12 +719,12 @@ struct CountRun {                     // device state shared by the count launch
 
 int count_run_begin(dfk_ctx* c, CountRun* R)
 {
-    int rc = c->alloc(R->d_hist, (uint64_t)HIST_GLOBAL_BINS * 8, "spectrum bins", true); if (rc) return rc;
-    rc = c->alloc(R->d_g, sizeof(CountGlobals), "count globals", true); if (rc) return rc;
+    int rc = c->alloc(R->d_hist, (uint64_t)HIST_GLOBAL_BINS * 8, "spectrum bins", Place::Low); if (rc) return rc;
+    rc = c->alloc(R->d_g, sizeof(CountGlobals), "count globals", Place::Low); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(R->d_hist.p, 0, (uint64_t)HIST_GLOBAL_BINS * 8, c->stream));
     HIP_TRY(hipMemsetAsync(R->d_g.p, 0, sizeof(CountGlobals), c->stream));
     R->g = (CountGlobals*)R->d_g.p; R->hist = (unsigned long long*)R->d_hist.p;
-    return c->alloc(R->d_snap, (uint64_t)HIST_GLOBAL_BINS * 8 + 256, "spectrum snapshot", true);
+    return c->alloc(R->d_snap, (uint64_t)HIST_GLOBAL_BINS * 8 + 256, "spectrum snapshot", Place::Low);
 }
 
 int count_snapshot(dfk_ctx* c, CountRun* R, bool restore)
@@ -1190,9 +1067,7 @@ int count_split(dfk_ctx* c, const Partition& P, const std::vector<ItemRange>& bu
     if (!singles.empty()) { rc = launch_count_big<K, NBC>(c, P2, singles, R); if (rc) return undo(rc); }
     HIP_TRY(hipStreamSynchronize(c->stream));
     // (everything allocated here goes back except R.big, the HBM path's output, which count_run collects)
-    const DevBuf keep_big = R.big;
-    for (size_t i = c->owned.size(); i-- > 0;)
-        if (c->owned[i].seq > mark && c->owned[i].p != keep_big.p) { DevBuf b; b.p = c->owned[i].p; b.bytes = c->owned[i].bytes; c->release(b); }
+    c->release_since(mark, &R.big);
     return 0;
 }
 
@@ -1201,16 +1076,6 @@ int count_split(dfk_ctx* c, const Partition& P, const std::vector<ItemRange>& bu
 // barcodes a table slot remembers: max(1, MIN_BC - 1); 0 without barcodes
 int barcode_words(const dfk_ctx* c, bool have_bc)
 { return !have_bc ? 0 : (int)std::max<uint32_t>(1, std::min<uint32_t>(c->cfg.min_bc, DFK_MAX_MIN_BC) - (c->cfg.min_bc > 1 ? 1 : 0)); }
-
-// solid k-mers a pass of n_inst instances is expected to emit at most (what its part's reservation is sized for)
-uint64_t solid_cap(const dfk_ctx* c, const CountRun& R, uint64_t n_inst)
-{
-    uint64_t cap = n_inst / std::max<uint32_t>(1, c->cfg.min_freq) + 1;
-    // (buckets are hash-distributed: once a pass has been counted the solid/instance ratio holds to a fraction of a percent)
-    if (R.inst_seen) cap = std::min<uint64_t>(cap, (uint64_t)(1.12 * (double)R.solid_seen / (double)R.inst_seen * (double)n_inst) + 65536);
-    else cap = std::min<uint64_t>(cap, n_inst / 10 + (1u << 20));   // first pass: a prior (30x data: n_inst/15, 58x: n_inst/28); too small -> redone
-    return cap;
-}
 
 template <int K> constexpr uint64_t out_chunk() { return 2ull << CountCfg<K>::LOG2S; }   // = table_finish's OUT_CHUNK
 
@@ -1224,8 +1089,7 @@ int count_prepare(dfk_ctx* c, const Partition& P, CountRun& R, int nbc)
     // Every solid k-mer has >= min_freq instances, which bounds the total; after the first pass the observed
     // solid/instance ratio holds to a fraction of a percent (buckets are hash-distributed).
     R.grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(P.n_items, count_grid<K>(c, nbc)));
-    uint64_t res = solid_cap(c, R, P.n_inst);
-    if (R.inst_seen) res = std::min<uint64_t>(res, (uint64_t)(1.10 * (double)R.solid_seen / (double)R.inst_seen * (double)P.n_inst) + 65536);
+    uint64_t res = part_entries(P.n_inst, c->cfg.min_freq, R.inst_seen, R.solid_seen);
     res = (res << attempt) + (uint64_t)R.grid * out_chunk<K>();       // + the chunk ends the workgroups leave empty
     const uint64_t room = c->budget > c->held ? (c->budget - c->held) : 0;
     if (res * 32 > room) res = room / 32;
@@ -1237,7 +1101,7 @@ int count_prepare(dfk_ctx* c, const Partition& P, CountRun& R, int nbc)
     R.cp = CountParams{c->cfg.min_freq, c->cfg.min_bc, 0, 0, res, c->cfg.min_freq > 1 ? 1u : 0u,
                        (c->cfg.flags & DFK_F_KEEP_PRE_ADJ) ? 1u : 0u};
     R.big_cap = 0;
-    rc = c->alloc(R.d_part, std::max<uint64_t>(1, res) * 32, "solid k-mer entries", true); if (rc) return rc;
+    rc = c->alloc(R.d_part, std::max<uint64_t>(1, res) * 32, "solid k-mer entries", Place::Low); if (rc) return rc;
     R.seg = (uint4*)R.d_part.p;
     return 0;
 }
@@ -1582,104 +1446,13 @@ uint32_t pick_log2_nb(uint64_t n_inst, uint32_t log2_world)
     return std::min<uint32_t>(l, 28);
 }
 
-// How many fine buckets the next pass may take, from what is free now.  A pass holds its bucket tables, its
-// records (32 B each) and its dense part of the dictionary (reserved when the pass is counted); the parts of
-// earlier passes stay resident, so later passes are smaller.  Buckets are hash-distributed, so a range holds
-// its share of the records and instances to within a fraction of a percent.
-// `running` != null: the range is scattered while that pass is being counted, so (1) its tables and records
-// must fit beside everything the running pass holds, and (2) its part must fit once the running pass has been
-// released.
-struct RunningPass { uint64_t bytes_held; uint64_t n_inst; uint32_t n_buckets; uint64_t block_off; };
-
-// The same question asked of the arena's actual free blocks (one chunk).  A pass block goes to the highest free
-// block that holds it -- now, beside the running pass.  The reservation for its part is made later, when the
-// running pass's block is gone, and goes to the lowest free block (the dictionary grows upwards): it has to fit
-// there, or it lands higher up and cuts the room of later blocks.  Largest n for which both hold, by bisection.
-double fit_free_blocks(const dfk_ctx* c, double per_block, double per_res, const RunningPass& run)
+// the numbers plan_range (dfk_arena.h) works from
+PlanInputs plan_inputs(const dfk_ctx* c, const BucketTable& T, const CountRun& R, uint32_t sub_nb, uint32_t lo, bool overlap)
 {
-    if (c->chunks.size() != 1 || c->chunks[0].free_list.empty()) return 1e300;
-    const std::vector<dfk_ctx::Free>& fl = c->chunks[0].free_list;
-    auto feasible = [&](double n) {
-        const uint64_t B = (uint64_t)(per_block * n / 0.98) + 1;
-        size_t at = fl.size();
-        for (size_t i = fl.size(); i-- > 0;) if (fl[i].bytes >= B) { at = i; break; }
-        if (at == fl.size()) return false;
-        // free list once the running block is gone and the new block is in place (at the upper end of fl[at])
-        std::vector<dfk_ctx::Free> h(fl.begin(), fl.end());
-        h[at].bytes -= B;
-        h.push_back(dfk_ctx::Free{run.block_off, run.bytes_held});
-        std::sort(h.begin(), h.end(), [](const dfk_ctx::Free& a, const dfk_ctx::Free& b) { return a.off < b.off; });
-        uint64_t low_off = 0, low_bytes = 0; bool have = false;
-        for (const dfk_ctx::Free& f : h) {                             // the lowest run of adjacent free blocks
-            if (!f.bytes) continue;
-            if (!have) { low_off = f.off; low_bytes = f.bytes; have = true; }
-            else if (low_off + low_bytes == f.off) low_bytes += f.bytes;
-            else break;
-        }
-        return per_res * n <= 0.98 * (double)low_bytes;
-    };
-    double lo = 0.0, hi = 0.0;
-    for (const dfk_ctx::Free& f : fl) hi = std::max(hi, 0.98 * (double)f.bytes / per_block);
-    if (feasible(hi)) return hi;
-    for (int it = 0; it < 30; ++it) { const double mid = 0.5 * (lo + hi); if (feasible(mid)) lo = mid; else hi = mid; }
-    return lo;
-}
-
-uint32_t plan_range(const dfk_ctx* c, const BucketTable& T, const CountRun& R, uint32_t sub_nb, uint32_t lo, const RunningPass* running, bool overlap)
-{
-    const double room = c->budget > c->held ? (double)(c->budget - c->held) : 0.0;
-    const double inst_per = (double)T.n_inst / sub_nb, rec_per = (double)T.n_records / sub_nb;
-    // solid k-mers per instance: observed on the passes done so far, else the prior stage_count starts from
-    double ratio = R.inst_seen ? 1.12 * (double)R.solid_seen / (double)R.inst_seen : 1.0 / 10.0;
-    ratio = std::min(ratio, 1.0 / std::max<uint32_t>(1, c->cfg.min_freq));
-    const double per_in = 81.0 + 32.5 * rec_per;                                         // tables and records (as the pass block is sized)
-    const double per_seg = 0.0;                                                                       // (workgroups write straight into the part's reservation: nothing else per pass)
-    const double per_out = 32.0 * ratio * inst_per * (double)(1u << c->seg_attempt);                  // the part's reservation
-    const double fixed = 120e6;                                       // chunk ends left empty by the workgroups (67 MB), small tables
-    const double left = (double)(sub_nb - lo);
-    double fit;
-    if (!running) {
-        fit = room > fixed ? (room - fixed) / (per_in + per_out) : 0.0;
-        // more than one pass to go: leave room for the records of the next one, which is scattered while this
-        // one is counted (passes of equal or decreasing size also keep the arena from fragmenting: each new
-        // range fits the hole left by the pass before the running one)
-        if (c->plan_derate * fit < left && overlap) {
-            fit = room > fixed ? (room - fixed) / (2.0 * per_in + per_seg + per_out) : 0.0;
-            // the very first scatter has nothing to hide under: keep it short (its fixed cost, reading every
-            // summary, is paid anyway; a tenth of the buckets -- a sixteenth while k_count ran at 75 G instances/s
-            // and a range could grow by 1.3 from pass to pass -- measured: DFK_PLAN_FIRST / DFK_PLAN_GROWTH, tools/plan_sweep.sh)
-            static const double first_div = getenv("DFK_PLAN_FIRST") ? atof(getenv("DFK_PLAN_FIRST")) : 10.0;
-            if (lo == 0) fit = std::min(fit, (double)sub_nb / first_div / c->plan_derate);
-        }
-    } else {
-        const double now = room - fixed;                              // (the running pass's part is reserved already)
-        const double later = room + (double)running->bytes_held - fixed;
-        TRACE("plan: now %.1f%% later %.1f%% geometry %.1f%% balance %.1f%% (room %.1f GB, running block %.1f GB)",
-              100 * 0.9 * now / (per_in + per_seg) / sub_nb, 100 * later / (per_in + per_out) / sub_nb,
-              100 * fit_free_blocks(c, per_in + per_seg, per_out - per_seg, *running) / sub_nb,
-              100 * std::max(0.0, room + (double)running->bytes_held - fixed) / (2.0 * (per_in + per_seg) + (per_out - per_seg)) / sub_nb,
-              room / 1e9, running->bytes_held / 1e9);
-        if (g_trace) for (const dfk_ctx::Free& f : c->chunks[0].free_list) fprintf(stderr, "[dfk]   free %.2f GB at %.2f GB\n", f.bytes / 1e9, f.off / 1e9);
-        // (a range that does not fit beside the running pass loses the overlap: plan it with more slack --
-        // the free room is in several pieces by now)
-        fit = std::max(0.0, std::min(0.9 * now / (per_in + per_seg), later / (per_in + per_out)));
-        fit = std::min(fit, fit_free_blocks(c, per_in + per_seg, per_out - per_seg, *running) / c->plan_derate);
-        // and leave the pass after this one (planned while this one is counted, the running one gone by then)
-        // a block of the same size: greedy ranges alternate between huge and tiny
-        fit = std::min(fit, std::max(0.0, room + (double)running->bytes_held - fixed) / (2.0 * (per_in + per_seg) + (per_out - per_seg)));
-    }
-    double n = c->plan_derate * fit;
-    // the range is scattered while the running pass is counted: no larger than what that count hides (beside
-    // k_count a sweep moves a range's records about 1.15 times as fast as k_count counts them -- 8.3 ms against 9.6 ms
-    // per percent of the human-scale set's buckets -- after ~10 ms of reading masks; with 1.3, the value from when
-    // k_count ran at 75 G instances/s, the first three counts each waited 13-18 ms for the records of the next)
+    static const double first_div = getenv("DFK_PLAN_FIRST") ? atof(getenv("DFK_PLAN_FIRST")) : 10.0;
     static const double growth = getenv("DFK_PLAN_GROWTH") ? atof(getenv("DFK_PLAN_GROWTH")) : 1.1;
-    if (running && overlap) n = std::min(n, growth * (double)running->n_buckets);
-    if (left <= 0.99 * fit && left < 1.06 * n) n = left;              // no sliver of a last pass if the rest (almost certainly) fits
-    else if (left > n && left < 1.3 * n) n = 0.5 * left + 1.0;        // two even passes rather than a big one and a sliver (1.7 while the cliff of section 9 was unexplained: a big count beside a small sweep)
-    n = std::min(n, left);
-    if (n < 16.0) return running ? 0u : (uint32_t)std::min(16.0, left);
-    return (uint32_t)n;
+    return PlanInputs{c->budget > c->held ? (double)(c->budget - c->held) : 0.0, sub_nb, lo, T.n_inst, T.n_records, R.inst_seen, R.solid_seen,
+                      c->cfg.min_freq, c->seg_attempt, c->plan_derate, overlap, first_div, growth, g_trace};
 }
 
 struct StreamSwap {                                    // run a stretch of host code against the second stream
@@ -1726,7 +1499,7 @@ int run_typed(dfk_ctx* c, const Inputs& in, Prescan* pre = nullptr)
     const bool overlap = getenv("DFK_NO_OVERLAP") == nullptr;
     uint32_t n_passes = 0, retries = 0;
     c->seg_attempt = 0; c->distinct_per_inst = 0.0;
-    struct Job { ScatterJob sj; dfk_ctx::PassBlock blk; uint64_t mark = 0; bool valid = false; };
+    struct Job { ScatterJob sj; Arena::PassBlock blk; uint64_t mark = 0; bool valid = false; };
     Job cur, nxt;
     auto drop_events = [&](Job& j) { if (j.sj.e0) { (void)hipEventDestroy(j.sj.e0); (void)hipEventDestroy(j.sj.e1); j.sj.e0 = j.sj.e1 = nullptr; } };
     // start the scatter of [lo, lo + n) on the second stream; NOMEM leaves nothing behind
@@ -1745,17 +1518,9 @@ int run_typed(dfk_ctx* c, const Inputs& in, Prescan* pre = nullptr)
         j.sj = ScatterJob{}; j.mark = c->alloc_seq; j.valid = false;
         const bool defer = may_defer && (double)n < defer_below * (double)sub_nb;
         TRACE("pass range [%u, %u) of %u (%.1f %%), %.2f GB held of %.2f", lo, lo + n, sub_nb, 100.0 * n / sub_nb, c->held / 1e9, c->budget / 1e9);
-        // the pass's block: tables (80 B per bucket with their scratch) and records (an estimate: what does not
-        // fit the block falls back to the open arena)
-        const double share = (double)n / sub_nb;
-        const uint64_t blk_bytes = (uint64_t)(1.01 * (80.0 * n + 32.0 * share * (double)T.n_records)) + (16ull << 20);
-        j.blk = dfk_ctx::PassBlock{};
-        int r = c->alloc(j.blk.block, blk_bytes, "pass block");
-        if (!r) {
-            c->sub = &j.blk;
-            { StreamSwap sw(c, c->stream2); r = scatter_begin<K>(c, in, T, 0, 0, lo, n, &j.sj, !defer); }
-            c->sub = nullptr;
-        }
+        j.blk = Arena::PassBlock{};
+        int r = c->alloc(j.blk.block, pass_block_bytes(n, sub_nb, T.n_records), "pass block");
+        if (!r) { Arena::Current in_blk(c->arena, j.blk); StreamSwap sw(c, c->stream2); r = scatter_begin<K>(c, in, T, 0, 0, lo, n, &j.sj, !defer); }
         if (r) { (void)hipStreamSynchronize(c->stream2); c->release_since(j.mark); drop_events(j); return r; }
         if (defer) { ScatterJob* sj = &j.sj; c->after_count_launch = [c, &in, &T, sj]() { return scatter_launch<K>(c, in, T, 0, 0, sj); }; TRACE("  (its sweep starts behind k_count)"); }
         j.valid = true;
@@ -1764,7 +1529,7 @@ int run_typed(dfk_ctx* c, const Inputs& in, Prescan* pre = nullptr)
     // the first range of a (re)started sequence: alone, shrinking until it fits
     auto start_alone = [&](Job& j, uint32_t lo) -> int {
         for (;;) {
-            const uint32_t n = forced ? std::min(per_forced, sub_nb - lo) : plan_range(c, T, R, sub_nb, lo, nullptr, overlap);
+            const uint32_t n = forced ? std::min(per_forced, sub_nb - lo) : plan_range(plan_inputs(c, T, R, sub_nb, lo, overlap), c->arena.free_blocks(), nullptr);
             // a budget that leaves room for slivers only would take thousands of passes: say so instead
             if (!forced && n < sub_nb - lo && (uint64_t)n * 1024 < sub_nb)
                 return fail(DFK_E_NOMEM, "HBM budget too small: %.2f GB free of %.2f GB allows passes of %u of %u buckets",
@@ -1781,15 +1546,13 @@ int run_typed(dfk_ctx* c, const Inputs& in, Prescan* pre = nullptr)
         rc = scatter_end<K>(c, in, T, 0, 0, &cur.sj); if (rc) return rc;
         const dfk_stats st0 = c->st;
         rc = count_snapshot(c, &R, false); if (rc) return rc;
-        c->sub = &cur.blk;
-        rc = count_prepare<K>(c, cur.sj.P, R, barcode_words(c, in.bc != nullptr));
-        c->sub = nullptr;
+        { Arena::Current in_blk(c->arena, cur.blk); rc = count_prepare<K>(c, cur.sj.P, R, barcode_words(c, in.bc != nullptr)); }
         nxt.valid = false;
         if (!rc && overlap && nlo < sub_nb) {
             const Partition& P = cur.sj.P;
             (void)P;
-            const RunningPass rp{cur.blk.block.bytes, cur.sj.P.n_inst, n, (uint64_t)((char*)cur.blk.block.p - c->chunks[0].p)};
-            const uint32_t n2 = forced ? std::min(per_forced, sub_nb - nlo) : plan_range(c, T, R, sub_nb, nlo, &rp, overlap);
+            const RunningPass rp{cur.blk.block.bytes, cur.sj.P.n_inst, n, c->arena.offset_of(cur.blk.block)};
+            const uint32_t n2 = forced ? std::min(per_forced, sub_nb - nlo) : plan_range(plan_inputs(c, T, R, sub_nb, nlo, overlap), c->arena.free_blocks(), &rp);
             if (n2) {
                 const int r2 = start(nxt, nlo, n2, true);
                 if (r2 && r2 != DFK_E_NOMEM) return r2;                // NOMEM: this range is scattered after the count instead
@@ -1875,7 +1638,7 @@ int run_under_upload(dfk_ctx* c, const Inputs& in, const uint8_t* h_packed)
     const uint64_t stride = std::max<uint64_t>(1, (n + 32767) / 32768), n_samp = n / stride + 2;
     std::vector<uint64_t> samp(n_samp);
     {
-        DevBuf d; int rc = c->alloc(d, n_samp * 8, "offset samples", true); if (rc) return rc;
+        DevBuf d; int rc = c->alloc(d, n_samp * 8, "offset samples", Place::Low); if (rc) return rc;
         hipLaunchKernelGGL(k_sample_u64, dim3((unsigned)((n_samp + 255) / 256)), dim3(256), 0, c->stream, in.base_off, stride, n, n_samp, (uint64_t*)d.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(samp.data(), d.p, n_samp * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2219,6 +1982,7 @@ int dfk_create(const dfk_config* cfg, dfk_ctx** out)
     // not exist.
     const uint64_t cap = (uint64_t)(0.9 * (double)fr);
     c->budget = cfg->hbm_budget_bytes ? std::min<uint64_t>(cfg->hbm_budget_bytes, cap) : cap;
+    c->arena.trace = g_trace;
     if (cfg->hbm_budget_bytes > cap)
         TRACE("hbm_budget_bytes %.1f GB is more than 90 %% of the free HBM: clamped to %.1f GB", cfg->hbm_budget_bytes / 1e9, cap / 1e9);
     *out = c;

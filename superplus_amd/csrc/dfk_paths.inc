@@ -193,8 +193,8 @@ int paths_build_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in)
         DevBuf slots, slot_off;
         bool again = false;
         for (;;) {                                                              // shrink until the real scratch fits
-            rc = c->alloc(slots, (nb + 1) * 8, "path slots", true); if (rc) return rc;
-            rc = c->alloc(slot_off, (nb + 1) * 8, "path slot offsets", true); if (rc) return rc;
+            rc = c->alloc(slots, (nb + 1) * 8, "path slots", Place::Low); if (rc) return rc;
+            rc = c->alloc(slot_off, (nb + 1) * 8, "path slot offsets", Place::Low); if (rc) return rc;
             const unsigned grid = (unsigned)std::min<uint64_t>((nb + 255) / 256, 16ull * cus);
             hipLaunchKernelGGL(k_path_slots, dim3(grid), dim3(256), 0, c->stream, in.read_len, r0, nb, (uint32_t)K, cap, (uint64_t*)slots.p);
             HIP_TRY(hipMemsetAsync((uint64_t*)slots.p + nb, 0, 8, c->stream));
@@ -208,12 +208,12 @@ int paths_build_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in)
                 c->release(slots);
                 DevBuf parts, path, quals, o_off, o_len, o_first, sizes, size_off;
                 PathBatch B; B.r0 = r0; B.n = nb; B.file_base = file_at;
-                if ((rc = c->alloc(parts, std::max<uint64_t>(1, total) * sizeof(PartD), "path parts", true)) ||
-                    (rc = c->alloc(path, (2 * total + 2 * nb) * 4, "path room", true)) ||
-                    (rc = c->alloc(quals, qtotal + 64, "decoded qualities", true)) ||
-                    (rc = c->alloc(o_off, nb * 4, "path offsets", true)) || (rc = c->alloc(o_len, nb * 4, "path lengths", true)) ||
-                    (rc = c->alloc(o_first, nb * 4, "path starts", true)) ||
-                    (rc = c->alloc(sizes, (nb + 1) * 8, "element sizes", true)) || (rc = c->alloc(size_off, (nb + 1) * 8, "element offsets", true)))
+                if ((rc = c->alloc(parts, std::max<uint64_t>(1, total) * sizeof(PartD), "path parts", Place::Low)) ||
+                    (rc = c->alloc(path, (2 * total + 2 * nb) * 4, "path room", Place::Low)) ||
+                    (rc = c->alloc(quals, qtotal + 64, "decoded qualities", Place::Low)) ||
+                    (rc = c->alloc(o_off, nb * 4, "path offsets", Place::Low)) || (rc = c->alloc(o_len, nb * 4, "path lengths", Place::Low)) ||
+                    (rc = c->alloc(o_first, nb * 4, "path starts", Place::Low)) ||
+                    (rc = c->alloc(sizes, (nb + 1) * 8, "element sizes", Place::Low)) || (rc = c->alloc(size_off, (nb + 1) * 8, "element offsets", Place::Low)))
                     return rc;
                 HIP_TRY(hipMemsetAsync(ctr.p, 0, 32, c->stream));                // this batch's: reads placed, path edges, flags
                 const unsigned pgrid = (unsigned)std::min<uint64_t>((nb + 255) / 256, 64ull * cus);
@@ -262,7 +262,7 @@ int paths_build_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in)
     P->n_reads = n; P->n_placed = placed; P->n_edges = path_edges; P->var_total = file_at - 24; P->built = true;
     {   // dfk_paths_digest: the file's elements, whatever batches they were made in
         const unsigned dgrid = 32u * cus;                                       // (a slot pair per block, then the fold: see k_paths_digest)
-        DevBuf dg; rc = c->alloc(dg, 32 + 16ull * dgrid, "paths digest", true); if (rc) return rc;
+        DevBuf dg; rc = c->alloc(dg, 32 + 16ull * dgrid, "paths digest", Place::Low); if (rc) return rc;
         HIP_TRY(hipMemsetAsync(dg.p, 0, 32 + 16ull * dgrid, c->stream));
         unsigned long long* slots = (unsigned long long*)dg.p + 4;
         for (const PathBatch& b : P->batches)
@@ -471,7 +471,7 @@ int radix_sort_pairs(dfk_ctx* c, DevBuf k[2], DevBuf v[2], uint64_t n, uint32_t 
     const uint64_t n_tiles = (n + RS_TILE - 1) / RS_TILE;
     DevBuf hist, place;
     int rc;
-    if ((rc = c->alloc(hist, 256 * n_tiles * 8, "sort counts", true)) || (rc = c->alloc(place, 256 * n_tiles * 8, "sort places", true))) return rc;
+    if ((rc = c->alloc(hist, 256 * n_tiles * 8, "sort counts", Place::Low)) || (rc = c->alloc(place, 256 * n_tiles * 8, "sort places", Place::Low))) return rc;
     const unsigned sgrid = (unsigned)std::min<uint64_t>((n_tiles + RS_WAVES - 1) / RS_WAVES, 16ull * cus);
     for (uint32_t shift = 0; shift < bits; shift += 8) {
         hipLaunchKernelGGL(k_rs_hist, dim3(sgrid), dim3(64 * RS_WAVES), 0, c->stream, (const uint32_t*)k[*cur].p, n, shift, n_tiles, (uint64_t*)hist.p);
@@ -514,7 +514,7 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
     const uint64_t n_pairs = P->n_edges, n_he = G->he.size();
     if (!n_he) return fail(DFK_E_STATE, "the graph has no edges (the reference asserts the same, PathsIndex.cc:29)");
     const unsigned cus = (unsigned)c->prop.multiProcessorCount;
-    if (tail && (dir.empty() || !n_pairs || n_pairs >= (1ull << 31) || 8 * n_pairs > c->largest_allocatable() / 4 || c->alloc(tail->var, 8 * n_pairs, "a.paths.inv data", true))) tail = nullptr;
+    if (tail && (dir.empty() || !n_pairs || n_pairs >= (1ull << 31) || 8 * n_pairs > c->largest_allocatable() / 4 || c->alloc(tail->var, 8 * n_pairs, "a.paths.inv data", Place::Low))) tail = nullptr;
     const uint64_t mark = c->alloc_seq;
     int fd = -1;
     uint64_t had = 0;                                                    // bytes a.paths.inv had when it was opened (pages the caller made)
@@ -522,7 +522,7 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
         DevBuf counts, first, c64, eo, csb, d_inv;
         int rc;
         // ---- reads per edge, where each edge's list starts, the counts with the involuted edge's added
-        if ((rc = c->alloc(counts, n_he * 4, "reads per edge", true))) return rc;
+        if ((rc = c->alloc(counts, n_he * 4, "reads per edge", Place::Low))) return rc;
         HIP_TRY(hipMemsetAsync(counts.p, 0, n_he * 4, c->stream));
         uint64_t listed = 0;
         for (const PathBatch& b : P->batches) {
@@ -534,8 +534,8 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
         if (listed != n_pairs) return fail(DFK_E_HIP, "paths index: %llu path entries listed, %llu counted", (unsigned long long)listed, (unsigned long long)n_pairs);
         std::vector<int32_t> inv(n_he);
         for (size_t e = 0; e < n_he; ++e) inv[e] = G->he[e].rc ? G->fwd[G->he[e].ce] : G->rev[G->he[e].ce];
-        if ((rc = upload_vec(c, d_inv, inv, "involution")) || (rc = c->alloc(c64, (n_he + 1) * 8, "counts", true)) || (rc = c->alloc(first, (n_he + 1) * 8, "list starts", true)) ||
-            (rc = c->alloc(eo, (n_he + 1) * 8, "list offsets", true)) || (rc = c->alloc(csb, n_he * 4, "countsb", true))) return rc;
+        if ((rc = upload_vec(c, d_inv, inv, "involution")) || (rc = c->alloc(c64, (n_he + 1) * 8, "counts", Place::Low)) || (rc = c->alloc(first, (n_he + 1) * 8, "list starts", Place::Low)) ||
+            (rc = c->alloc(eo, (n_he + 1) * 8, "list offsets", Place::Low)) || (rc = c->alloc(csb, n_he * 4, "countsb", Place::Low))) return rc;
         const unsigned egrid = (unsigned)std::min<uint64_t>((n_he + 256) / 256, 32ull * cus);
         HIP_TRY(hipMemsetAsync(c64.p, 0, (n_he + 1) * 8, c->stream));
         hipLaunchKernelGGL(k_widen_u32, dim3(egrid), dim3(256), 0, c->stream, (const uint32_t*)counts.p, n_he, (uint64_t*)c64.p);
@@ -547,7 +547,7 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
         std::vector<uint64_t> h_first(n_he + 1);
         HIP_TRY(hipMemcpyAsync(h_first.data(), first.p, (n_he + 1) * 8, hipMemcpyDeviceToHost, c->stream));
         // dfk_paths_digest: where the lists start, the summed counts (the lists themselves range by range below)
-        DevBuf dg; if ((rc = c->alloc(dg, 128, "index digest", true))) return rc;
+        DevBuf dg; if ((rc = c->alloc(dg, 128, "index digest", Place::Low))) return rc;
         HIP_TRY(hipMemsetAsync(dg.p, 0, 128, c->stream));
         unsigned long long* d = (unsigned long long*)dg.p;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint64_t>), dim3(egrid), dim3(256), 0, c->stream, (const uint64_t*)first.p, n_he + 1, 0x2222ull, d + 4);
@@ -592,7 +592,7 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
             ++n_ranges;
             if (n_r) {
                 DevBuf k[2], v[2], var;
-                for (int i = 0; i < 2; ++i) { if ((rc = c->alloc(k[i], n_r * 4, "index keys", true)) || (rc = c->alloc(v[i], n_r * 4, "index reads", true))) return rc; }
+                for (int i = 0; i < 2; ++i) { if ((rc = c->alloc(k[i], n_r * 4, "index keys", Place::Low)) || (rc = c->alloc(v[i], n_r * 4, "index reads", Place::Low))) return rc; }
                 const bool whole = e0 == 0 && e1 == n_he;
                 if (tail && !whole) { c->release(tail->var); tail = nullptr; }      // (several ranges: each is written before the next is sorted)
                 uint64_t pair_base = 0;
@@ -604,7 +604,7 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
                         pair_base += b.var_bytes / 4 - 2 * b.n;
                     } else {
                         DevBuf n_in, at_of;
-                        if ((rc = c->alloc(n_in, (b.n + 1) * 8, "entries in the range", true)) || (rc = c->alloc(at_of, (b.n + 1) * 8, "their places", true))) return rc;
+                        if ((rc = c->alloc(n_in, (b.n + 1) * 8, "entries in the range", Place::Low)) || (rc = c->alloc(at_of, (b.n + 1) * 8, "their places", Place::Low))) return rc;
                         hipLaunchKernelGGL(k_pidx_range_count, dim3(grid), dim3(256), 0, c->stream, (const uint32_t*)b.var.p, (const uint32_t*)b.elem_off.p, b.n, b.var_bytes, (uint32_t)e0, (uint32_t)e1, (uint64_t*)n_in.p);
                         HIP_TRY(hipGetLastError());
                         rc = device_scan(c, (const uint64_t*)n_in.p, (uint64_t*)at_of.p, b.n + 1); if (rc) return rc;
@@ -628,7 +628,7 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
                                    (const uint32_t*)v[cur].p, n_r, 0x1111ull + h_first[e0], d);
                 HIP_TRY(hipGetLastError());
                 if (!dir.empty()) {
-                    if (!tail && (rc = c->alloc(var, n_r * 8, "a.paths.inv data", true))) return rc;
+                    if (!tail && (rc = c->alloc(var, n_r * 8, "a.paths.inv data", Place::Low))) return rc;
                     uint64_t* wide = (uint64_t*)(tail ? tail->var.p : var.p);
                     hipLaunchKernelGGL(k_widen_u32, dim3((unsigned)std::min<uint64_t>((n_r + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream, (const uint32_t*)v[cur].p, n_r, wide);
                     HIP_TRY(hipGetLastError());
@@ -692,7 +692,7 @@ int dups_write(dfk_ctx* c, PathState* P, const std::string& path, uint64_t* n_ma
     auto body = [&]() -> int {
         DevBuf dup, tk, tb, d_bad;
         int rc;
-        if ((rc = c->alloc(dup, std::max<uint64_t>(1, n_pairs), "duplicate marks", true)) || (rc = c->alloc(d_bad, 16, "dup check", true))) return rc;
+        if ((rc = c->alloc(dup, std::max<uint64_t>(1, n_pairs), "duplicate marks", Place::Low)) || (rc = c->alloc(d_bad, 16, "dup check", Place::Low))) return rc;
         HIP_TRY(hipMemsetAsync(dup.p, 0, std::max<uint64_t>(1, n_pairs), c->stream));
         HIP_TRY(hipMemsetAsync(d_bad.p, 0, 16, c->stream));
         // as many passes as the free HBM asks for: a pass's table holds the keys dealt to it at load <= 0.5
@@ -704,7 +704,7 @@ int dups_write(dfk_ctx* c, PathState* P, const std::string& path, uint64_t* n_ma
             slots = 1ull << std::max<uint32_t>(10, ceil_log2(2 * (P->n_placed / n_pass + P->n_placed / (4 * n_pass) + 1024)));   // (+25 %: the deal is by hash)
             if (16 * slots <= c->largest_allocatable() / 2 || n_pass >= 1024) break;
         }
-        if ((rc = c->alloc(tk, slots * 8, "duplicate keys", true)) || (rc = c->alloc(tb, slots * 8, "duplicate winners", true))) return rc;
+        if ((rc = c->alloc(tk, slots * 8, "duplicate keys", Place::Low)) || (rc = c->alloc(tb, slots * 8, "duplicate winners", Place::Low))) return rc;
         for (uint32_t pass = 0; pass < n_pass; ++pass) {
             hipLaunchKernelGGL(k_fill_u64, dim3(4096), dim3(256), 0, c->stream, (uint64_t*)tk.p, slots, ~0ull);
             HIP_TRY(hipMemsetAsync(tb.p, 0, slots * 8, c->stream));
@@ -726,7 +726,7 @@ int dups_write(dfk_ctx* c, PathState* P, const std::string& path, uint64_t* n_ma
         if (bad & 1u) return fail(DFK_E_ARG, "duplicate marking packs a read's first edge in 29 bits and its offset in 25: this graph does not fit");
         if (bad & 2u) return fail(DFK_E_HIP, "duplicate marking: a key vanished between its two passes");
         {   // dfk_paths_digest: which pairs are marked, and how many
-            DevBuf dg; if ((rc = c->alloc(dg, 32, "dup digest", true))) return rc;
+            DevBuf dg; if ((rc = c->alloc(dg, 32, "dup digest", Place::Low))) return rc;
             HIP_TRY(hipMemsetAsync(dg.p, 0, 32, c->stream));
             if (n_pairs) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint8_t>), dim3((unsigned)std::min<uint64_t>((n_pairs + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream,
                                             (const uint8_t*)dup.p, n_pairs, 0x4444ull, (unsigned long long*)dg.p);
@@ -769,7 +769,7 @@ void release_path_lookup(dfk_ctx* c, HostGraph* G) { c->release(G->d_index); c->
 template <int K>
 int paths_verify_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in, uint64_t* out)
 {
-    DevBuf ctr; int rc = c->alloc(ctr, 8 * PV_N + 8, "verify counters", true); if (rc) return rc;
+    DevBuf ctr; int rc = c->alloc(ctr, 8 * PV_N + 8, "verify counters", Place::Low); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(ctr.p, 0, 8 * PV_N + 8, c->stream));
     const unsigned cus = (unsigned)c->prop.multiProcessorCount;
     const unsigned g = (unsigned)std::min<uint64_t>((in.n_reads + 255) / 256, 32ull * cus);
@@ -957,7 +957,7 @@ int dfk_qual_hist(dfk_ctx* c, uint32_t max_len, int64_t* hist)
     std::fill(hist, hist + nd, 0);
     if (!n) return 0;
     DevBuf tab;
-    int rc = c->alloc(tab, nf * 8, "quality histogram", true); if (rc) return rc;
+    int rc = c->alloc(tab, nf * 8, "quality histogram", Place::Low); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(tab.p, 0, nf * 8, c->stream));
     const unsigned cus = (unsigned)c->prop.multiProcessorCount;
     const size_t lds = (size_t)2 * QH_Q * (QH_POS + 1) * 4;

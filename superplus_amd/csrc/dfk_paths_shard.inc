@@ -152,8 +152,8 @@ int dfk_shard_pidx_pairs(dfk_ctx* c, uint32_t world, const void** d_pairs, uint6
     if ((rc = c->alloc(S->pairs, np1 * 8, "index pairs to send"))) return rc;
     const uint64_t mark = c->alloc_seq;
     auto body = [&]() -> int {
-        for (int i = 0; i < 2; ++i) { if ((rc = c->alloc(k[i], np1 * 4, "index keys", true)) || (rc = c->alloc(v[i], np1 * 4, "index reads", true))) return rc; }
-        if ((rc = c->alloc(counts, n_he * 4, "reads per edge", true))) return rc;
+        for (int i = 0; i < 2; ++i) { if ((rc = c->alloc(k[i], np1 * 4, "index keys", Place::Low)) || (rc = c->alloc(v[i], np1 * 4, "index reads", Place::Low))) return rc; }
+        if ((rc = c->alloc(counts, n_he * 4, "reads per edge", Place::Low))) return rc;
         HIP_TRY(hipMemsetAsync(counts.p, 0, n_he * 4, c->stream));
         uint64_t pair_base = 0;
         for (const PathBatch& b : P->batches) {
@@ -210,8 +210,8 @@ int dfk_shard_pidx_write(dfk_ctx* c, uint32_t world, uint32_t rank, const void* 
         int rc;
         DevBuf k[2], v[2], cnt, var, d_bad;
         const uint64_t np1 = std::max<uint64_t>(1, n_in);
-        for (int i = 0; i < 2; ++i) { if ((rc = c->alloc(k[i], np1 * 4, "index keys", true)) || (rc = c->alloc(v[i], np1 * 4, "index reads", true))) return rc; }
-        if ((rc = c->alloc(cnt, std::max<uint64_t>(1, ne) * 4, "reads per edge", true)) || (rc = c->alloc(d_bad, 16, "index check", true))) return rc;
+        for (int i = 0; i < 2; ++i) { if ((rc = c->alloc(k[i], np1 * 4, "index keys", Place::Low)) || (rc = c->alloc(v[i], np1 * 4, "index reads", Place::Low))) return rc; }
+        if ((rc = c->alloc(cnt, std::max<uint64_t>(1, ne) * 4, "reads per edge", Place::Low)) || (rc = c->alloc(d_bad, 16, "index check", Place::Low))) return rc;
         HIP_TRY(hipMemsetAsync(cnt.p, 0, std::max<uint64_t>(1, ne) * 4, c->stream));
         HIP_TRY(hipMemsetAsync(d_bad.p, 0, 16, c->stream));
         if (n_in) hipLaunchKernelGGL(k_unpack_pairs, dim3((unsigned)std::min<uint64_t>((n_in + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream, (const uint64_t*)d_pairs_in, n_in,
@@ -227,12 +227,12 @@ int dfk_shard_pidx_write(dfk_ctx* c, uint32_t world, uint32_t rank, const void* 
         if (bad) return fail(DFK_E_HIP, "paths index: a pair arrived at a rank that does not own its edge");
         for (uint64_t e = 0; e < ne; ++e) if (hc[e] != counts_global[e0 + e]) return fail(DFK_E_HIP, "paths index: edge %llu received %u reads, the counts say %llu", (unsigned long long)(e0 + e), hc[e], (unsigned long long)counts_global[e0 + e]);
         c->release(k[0]); c->release(k[1]); c->release(v[cur ^ 1]);
-        if ((rc = c->alloc(var, np1 * 8, "a.paths.inv data", true))) return rc;
+        if ((rc = c->alloc(var, np1 * 8, "a.paths.inv data", Place::Low))) return rc;
         if (n_in) hipLaunchKernelGGL(k_widen_u32, dim3((unsigned)std::min<uint64_t>((n_in + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream, (const uint32_t*)v[cur].p, n_in, (uint64_t*)var.p);
         HIP_TRY(hipGetLastError());
         {   // digests of this rank's share (dfk_paths_digest; the caller adds / xors the ranks' words): positions and edges are the whole file's
             DevBuf dg, d_first;
-            if ((rc = c->alloc(dg, 128, "index digest", true)) || (rc = c->alloc(d_first, (ne + 1) * 8, "list starts", true))) return rc;
+            if ((rc = c->alloc(dg, 128, "index digest", Place::Low)) || (rc = c->alloc(d_first, (ne + 1) * 8, "list starts", Place::Low))) return rc;
             HIP_TRY(hipMemsetAsync(dg.p, 0, 128, c->stream));
             const uint64_t n_first = ne + (rank + 1 == world ? 1 : 0);      // (the last rank also holds the end of the last list)
             HIP_TRY(hipMemcpyAsync(d_first.p, first.data() + e0, n_first * 8, hipMemcpyHostToDevice, c->stream));
@@ -312,7 +312,7 @@ int dfk_shard_dup_keys(dfk_ctx* c, uint32_t world, const void** d_items, uint64_
     c->release(S->items); c->release(S->src);
     DevBuf cur, d_bad;
     int rc;
-    if ((rc = c->alloc(cur, 64 * 8, "dup cursors", true)) || (rc = c->alloc(d_bad, 16, "dup check", true))) return rc;
+    if ((rc = c->alloc(cur, 64 * 8, "dup cursors", Place::Low)) || (rc = c->alloc(d_bad, 16, "dup check", Place::Low))) return rc;
     HIP_TRY(hipMemsetAsync(cur.p, 0, 64 * 8, c->stream));
     HIP_TRY(hipMemsetAsync(d_bad.p, 0, 16, c->stream));
     auto sweep = [&](bool place) {
@@ -356,7 +356,7 @@ int dfk_shard_dup_answer(dfk_ctx* c, const void* d_items_in, uint64_t n_in, void
     const uint64_t slots = 1ull << std::max<uint32_t>(10, ceil_log2(2 * n_in + 1024));
     DevBuf tk, tb, d_bad;
     int rc;
-    if ((rc = c->alloc(tk, slots * 8, "duplicate keys", true)) || (rc = c->alloc(tb, slots * 8, "duplicate winners", true)) || (rc = c->alloc(d_bad, 16, "dup check", true))) return rc;
+    if ((rc = c->alloc(tk, slots * 8, "duplicate keys", Place::Low)) || (rc = c->alloc(tb, slots * 8, "duplicate winners", Place::Low)) || (rc = c->alloc(d_bad, 16, "dup check", Place::Low))) return rc;
     hipLaunchKernelGGL(k_fill_u64, dim3(4096), dim3(256), 0, c->stream, (uint64_t*)tk.p, slots, ~0ull);
     HIP_TRY(hipMemsetAsync(tb.p, 0, slots * 8, c->stream));
     HIP_TRY(hipMemsetAsync(d_bad.p, 0, 16, c->stream));
@@ -386,7 +386,7 @@ int dfk_shard_dup_write(dfk_ctx* c, const void* d_ans_back, uint64_t n, const ch
     const unsigned cus = (unsigned)c->prop.multiProcessorCount;
     DevBuf dup, dg;
     int rc;
-    if ((rc = c->alloc(dup, std::max<uint64_t>(1, n_pairs), "duplicate marks", true)) || (rc = c->alloc(dg, 32, "dup digest", true))) return rc;
+    if ((rc = c->alloc(dup, std::max<uint64_t>(1, n_pairs), "duplicate marks", Place::Low)) || (rc = c->alloc(dg, 32, "dup digest", Place::Low))) return rc;
     HIP_TRY(hipMemsetAsync(dup.p, 0, std::max<uint64_t>(1, n_pairs), c->stream));
     HIP_TRY(hipMemsetAsync(dg.p, 0, 32, c->stream));
     if (n) hipLaunchKernelGGL(k_dup_mark, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream, (const uint8_t*)d_ans_back, (const uint32_t*)S->src.p, n, (uint8_t*)dup.p);

@@ -105,7 +105,7 @@ int pbf_run(dfk_ctx* c, const dfk_pbf_input* in, dfk_pbf* R)
         for (uint64_t k0 = 0; k0 < n_reads; k0 += per_batch) {
             Batch B; B.k0 = k0; B.nk = std::min(per_batch, n_reads - k0);
             DevBuf ssz;
-            if ((rc = c->alloc(ssz, (B.nk + 1) * 8, "scratch sizes", true)) || (rc = c->alloc(B.soff, (B.nk + 1) * 8, "scratch offsets", true)) || (rc = c->alloc(B.nblk, B.nk * 4, "block counts", true))) return rc;
+            if ((rc = c->alloc(ssz, (B.nk + 1) * 8, "scratch sizes", Place::Low)) || (rc = c->alloc(B.soff, (B.nk + 1) * 8, "scratch offsets", Place::Low)) || (rc = c->alloc(B.nblk, B.nk * 4, "block counts", Place::Low))) return rc;
             hipLaunchKernelGGL(k_pbf_scratch_sizes, dim3(grid_for(B.nk + 1)), dim3(256), 0, c->stream, F, order, B.k0, B.nk, (uint64_t*)ssz.p);
             HIP_TRY(hipGetLastError());
             rc = device_scan(c, (const uint64_t*)ssz.p, (uint64_t*)B.soff.p, B.nk + 1); if (rc) return rc;
@@ -113,7 +113,7 @@ int pbf_run(dfk_ctx* c, const dfk_pbf_input* in, dfk_pbf* R)
             HIP_TRY(hipMemcpyAsync(&words, (uint64_t*)B.soff.p + B.nk, 8, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             c->release(ssz);
-            if ((rc = c->alloc(B.scratch, std::max<uint64_t>(1, words) * 4, "encoder scratch", true))) return rc;
+            if ((rc = c->alloc(B.scratch, std::max<uint64_t>(1, words) * 4, "encoder scratch", Place::Low))) return rc;
             if (std::max(max_len[0], max_len[1]) <= PBF_LDS_LEN)
                 hipLaunchKernelGGL(k_pbf_pq_plan_lds, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((B.nk + 63) / 64, 64ull * cus))), dim3(64), 0, c->stream, F, order, B.k0, B.nk,
                                    (const uint64_t*)B.soff.p, (uint32_t*)B.scratch.p, (uint32_t*)B.nblk.p, (uint64_t*)pq_sz.p + B.k0, bad);

@@ -262,7 +262,7 @@ int shard_count_typed(dfk_ctx* c, const void* d_records, uint64_t n_records, uin
     S->run_open = false;
     if (c->parts.size() > 1) {
         dfk_ctx::Part all; all.n = c->n_solid;
-        rc = c->alloc(all.buf, all.n * 32, "merged solid k-mer entries", false); if (rc) return rc;
+        rc = c->alloc(all.buf, all.n * 32, "merged solid k-mer entries"); if (rc) return rc;
         uint64_t at = 0;
         for (dfk_ctx::Part& pt : c->parts) {
             if (pt.n) HIP_TRY(hipMemcpyAsync((char*)all.buf.p + 32 * at, pt.buf.p, 32 * pt.n, hipMemcpyDeviceToDevice, c->stream));
