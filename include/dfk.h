@@ -60,6 +60,7 @@ typedef struct dfk_config {
 
 #define DFK_F_KEEP_PRE_ADJ   1u   /* also keep contexts before recomputeAdjacencies (kmers.kvec view) */
 #define DFK_F_KEEP_INPUTS    2u   /* dfk_count keeps its device copies of the reads (for dfk_paths_build) until the next count */
+#define DFK_F_MARK_BADS 4u        /* dfk_paths_build* also gathers MarkBads' per-read sums (dfk_bads_*); set at dfk_create */
 
 /* 32-byte image of KmerDictEntry<K> (kmers/ReadPather.h:105-146,169-195):
  * w0 = bases 0..31 MSB-first, w1 = remaining bases left-aligned (kmers/KMer.h:154-160),
@@ -87,7 +88,7 @@ typedef struct dfk_stats {
      * context's stream */
     float ms_upload, ms_trim, ms_part_count, ms_part_scatter, ms_count, ms_fallback, ms_adjacency, ms_total;
     uint64_t hbm_bytes_peak;    /* peak device bytes held by the context */
-    uint64_t reserved[8];       /* [0] = passes used, [1..3] = microseconds (graph device, graph host, pathing), [4] = gate timeouts, [5] = device bytes held now, [6] = launches of the counting scan */
+    uint64_t reserved[8];       /* [0] = passes used, [1..3] = microseconds (graph device, graph host, pathing), [4] = gate timeouts, [5] = device bytes held now, [6] = launches of the counting scan, [7] = microseconds of the pathing spent in k_bad_sums (DFK_F_MARK_BADS) */
 } dfk_stats;
 
 typedef struct dfk_ctx dfk_ctx;
@@ -277,6 +278,27 @@ int dfk_dups_write(dfk_ctx* ctx, const char* path, uint64_t* n_marked_pairs);
  * the device and entering the file while the duplicates are marked (when the index is built in one range; otherwise exactly the
  * two calls above). */
 int dfk_paths_index_dups_write(dfk_ctx* ctx, const char* dir, const char* dup_path, uint64_t* n_marked_pairs);
+
+/* ---- the first step of the reference's patching stage: MarkBads (10X/SecretOps.cc:71-109, called by StagePatch,
+ * 10X/runstages/RunStages.cc:196-200; written as a.<K>/a.bad, 10X/DF.cc:604) ----
+ * Every placed read is laid over the concatenation of its path's edges (hb.Cat: K-1 bases shared between neighbours) at its
+ * offset; the qualities of the whole read's bases that disagree with the graph, where the two overlap, are added up, and a
+ * PAIR is bad when the sum of either of its reads is strictly greater than 150.  The reference reopens .qualp from disk for
+ * this; here the sums are gathered by dfk_paths_build* while a batch's reads, qualities, edges and finished paths are on the
+ * device together (k_bad_sums, csrc/dfk_paths_kernels.h) -- on a context created with DFK_F_MARK_BADS; without the flag the
+ * build launches and allocates nothing for it and the three calls return DFK_E_STATE.
+ *   dfk_bads_sums        the per-read sums (saturated at 65535, 0 for a read without a path), for tests
+ *   dfk_bads_write       folds the sums to a byte per pair on the device, writes a.bad ("BINWRITE" | u64 pairs | the bytes) and
+ *                        returns the number marked; path NULL = everything but the file; digest (or NULL) = sum and xor over the
+ *                        reads of h(whole-set read id, sum), so that two runs are compared without fetching: the shares of a
+ *                        sharded run's ranks add / xor.  An odd number of reads is DFK_E_ARG, as for dfk_dups_write.
+ *   dfk_bads_write_part  a rank's bytes at pair first_pair of a file of total_pairs (the rank with first_pair == 0 writes the
+ *                        header), like dfk_shard_dup_write
+ * Valid from dfk_paths_build until the paths are dropped (the next build or graph), before or after dfk_paths_index_write /
+ * dfk_dups_write: they need neither the reads nor the k-mer index. */
+int dfk_bads_sums(dfk_ctx* ctx, uint16_t* out, uint64_t cap);
+int dfk_bads_write(dfk_ctx* ctx, const char* path, uint64_t* n_marked_pairs, uint64_t* digest /* [2] or NULL */);
+int dfk_bads_write_part(dfk_ctx* ctx, const char* path, uint64_t first_pair, uint64_t total_pairs, uint64_t* n_marked, uint64_t* digest /* [2] or NULL */);
 
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).

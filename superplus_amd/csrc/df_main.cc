@@ -354,6 +354,13 @@ void print_digests(dfk_ctx* ctx, const uint64_t* whole_run = nullptr)
            (unsigned long long)w[DFK_CK_EDGE_KMERS], (unsigned long long)w[DFK_CK_N_SOLID], (unsigned long long)w[DFK_CK_INV_VIOLATIONS], (unsigned long long)w[DFK_CK_N_EDGES]);
 }
 
+// BADS=True: MarkBads' own line (10X/SecretOps.cc:108-109) and a machine-readable one beside DF_DIGESTS (whose keys stay as they are)
+void print_bads(uint64_t n_bad, uint64_t n_pairs, const uint64_t* digest)
+{
+    printf("%.3f%% of pairs marked bad\n", n_pairs ? 100.0 * (double)n_bad / (double)n_pairs : 0.0);
+    printf("DF_BADS {\"a.bad\": \"%016llx%016llx\", \"bad_pairs\": %llu}\n", (unsigned long long)digest[0], (unsigned long long)digest[1], (unsigned long long)n_bad);
+}
+
 int rank_main(std::map<std::string, std::string>& a, unsigned K, const std::string& work_dir, const std::string& head, int rank, int world,
               dfkx::LoopbackHub* hub)
 {
@@ -386,6 +393,8 @@ int rank_main(std::map<std::string, std::string>& a, unsigned K, const std::stri
         cfg.minimizer_len = (uint32_t)atoi(a["MINIMIZER"].c_str());
         cfg.hbm_budget_bytes = (uint64_t)(atof(a["HBM_GB"].c_str()) * 1073741824.0);
         if (truthy(a["GRAPH"]) && truthy(a["PATHS"])) cfg.flags |= DFK_F_KEEP_INPUTS;      // the rank's staged reads stay for pathReads
+        const bool want_bads = truthy(a["GRAPH"]) && truthy(a["PATHS"]) && truthy(a["BADS"]);
+        if (want_bads) cfg.flags |= DFK_F_MARK_BADS;                                        // ... and MarkBads' sums are gathered while they are pathed
         if (hub && !cfg.hbm_budget_bytes) { size_t fr = 0, tot = 0; (void)hipSetDevice(cfg.device); (void)hipMemGetInfo(&fr, &tot); cfg.hbm_budget_bytes = (uint64_t)(0.8 * (double)fr / world); }   // ranks sharing one GPU
         dfk_ctx* ctx = nullptr;
         if (dfk_create(&cfg, &ctx)) throw std::runtime_error(dfk_last_error());
@@ -454,12 +463,13 @@ int rank_main(std::map<std::string, std::string>& a, unsigned K, const std::stri
                 t0 = now_s();
                 if (rank == 0) printf("%s: pathing reads\n", date().c_str());
                 uint64_t words[DFK_CHECK_WORDS] = {};
-                dfkx::shard_paths_index_dups(ctx, *T, dir, lo, fb.n, piece, &pt, words);
+                dfkx::shard_paths_index_dups(ctx, *T, dir, lo, fb.n, piece, &pt, words, want_bads);
                 p_placed = pt.placed;
                 t_paths = now_s() - t0;
                 if (rank == 0) {
                     printf("%.2f%% of pairs appear to be duplicates\n", fb.n ? 100.0 * (double)pt.dup_pairs / (double)(fb.n / 2) : 0.0);
                     print_digests(ctx, words);
+                    if (want_bads) print_bads(pt.bad_pairs, fb.n / 2, pt.bad_digest);
                 }
             }
             if (graph_writer.joinable()) graph_writer.join();
@@ -541,7 +551,7 @@ int main(int argc, char** argv)
     std::map<std::string, std::string> a = {
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
-        {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}};
+        {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"}};
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -772,6 +782,8 @@ int main(int argc, char** argv)
         // GRAPH=False, where it is the one way the dictionary leaves this process
         const bool want_kvec = a["KVEC"] == "Auto" ? (!truthy(a["GRAPH"]) || truthy(a["KVEC_SORTED"])) : truthy(a["KVEC"]);
         if (want_paths) cfg.flags |= DFK_F_KEEP_INPUTS;                          // the reads stay on the device for pathReads
+        const bool want_bads = want_paths && truthy(a["BADS"]);
+        if (want_bads) cfg.flags |= DFK_F_MARK_BADS;                             // ... and MarkBads' sums are gathered while they are pathed
         // a.<K>/a.paths and a.paths.inv are the stage's largest outputs (20-odd and 8 bytes a read: 37 and 14 GB at configs[1]) and
         // their sizes are known only once the reads are pathed.  Pages for them are made NOW (PATHS_RESERVE bytes a read for
         // a.paths -- 16 fixed and one path entry -- and 8 for every entry that leaves for a.paths.inv; 0 = don't), by threads nobody
@@ -976,6 +988,11 @@ int main(int argc, char** argv)
                 t_paths = now_s() - t0;
                 printf("%.2f%% of pairs appear to be duplicates\n", n_reads ? 100.0 * (double)n_dup / (double)(n_reads / 2) : 0.0);
                 print_digests(ctx);
+                if (want_bads) {                                               // MarkBads (StagePatch, RunStages.cc:196-200): a.<K>/a.bad, after the index and the duplicate marks
+                    uint64_t n_bad = 0, bd[2] = {0, 0};
+                    if (dfk_bads_write(ctx, (dir + "/a.bad").c_str(), &n_bad, bd)) throw std::runtime_error(dfk_last_error());
+                    print_bads(n_bad, n_reads / 2, bd);
+                }
             }
             t_g_write = tw_graph;
         }

@@ -251,14 +251,14 @@ inline uint64_t shard_allgather_dict(dfk_ctx* ctx, Transport& T, uint64_t piece)
     return total;
 }
 
-struct ShardPathTimes { double paths = 0, paths_write = 0, index = 0, dups = 0; uint64_t placed = 0, path_edges = 0, dup_pairs = 0; };
+struct ShardPathTimes { double paths = 0, paths_write = 0, index = 0, dups = 0; uint64_t placed = 0, path_edges = 0, dup_pairs = 0, bad_pairs = 0, bad_digest[2] = {0, 0}; };
 
 // Rows f-2 and f-4 on every rank (dfk.h, "rows f-2 / f-4 of a multi-GPU run"): the rank's pair range pathed and written into its
 // place in a.paths; the paths index by one all-to-all of (edge, read) pairs to the owners of the edge ranges; the duplicate marks
 // by one all-to-all of keys to the owners of their hash and one of answers back.  first_read / total_reads: this rank's pair
 // range in the whole set.  digest[DFK_CHECK_WORDS]: the whole run's words (sums added, xors xored over the ranks).
 inline void shard_paths_index_dups(dfk_ctx* ctx, Transport& T, const std::string& dir, uint64_t first_read, uint64_t total_reads, uint64_t piece,
-                                   ShardPathTimes* tm, uint64_t* digest)
+                                   ShardPathTimes* tm, uint64_t* digest, bool bads = false)
 {
     using clock = std::chrono::steady_clock;
     auto secs = [](clock::time_point a) { return std::chrono::duration<double>(clock::now() - a).count(); };
@@ -338,6 +338,16 @@ inline void shard_paths_index_dups(dfk_ctx* ctx, Transport& T, const std::string
     } catch (...) { (void)hipFree(d_items); (void)hipFree(d_ans); (void)hipFree(d_back); throw; }
     (void)hipFree(d_items); (void)hipFree(d_ans); (void)hipFree(d_back);
     tm->dups = secs(t0);
+    // ---- MarkBads (BADS=True; the contexts were created with DFK_F_MARK_BADS): the sums were gathered while the rank pathed its
+    //      reads, so every rank only folds them and writes its pairs' bytes of a.bad; the counts add, the digests add / xor
+    if (bads) {
+        uint64_t part[3] = {0, 0, 0};
+        note(dfk_bads_write_part(ctx, (dir + "/a.bad").c_str(), first_read / 2, total_reads / 2, &part[0], &part[1]));
+        agree("dfk_bads_write_part");
+        std::vector<uint64_t> parts(3 * (size_t)w);
+        T.all_gather(part, 3, parts.data());
+        for (int s = 0; s < w; ++s) { tm->bad_pairs += parts[3 * s]; tm->bad_digest[0] += parts[3 * s + 1]; tm->bad_digest[1] ^= parts[3 * s + 2]; }
+    }
     // ---- the run's digests: every rank's share, sums added and xors xored
     uint64_t wds[DFK_CHECK_WORDS] = {};
     note(dfk_paths_digest(ctx, wds));

@@ -33,6 +33,7 @@ struct PathState {
     std::vector<PathBatch> batches;
     uint64_t n_reads = 0, n_placed = 0, n_edges = 0, var_total = 0;
     DevBuf digest;                                    // u32[n_reads]: first five bases | quality sum << 10 (k_read_digest), for MarkDups
+    DevBuf bad_sums;                                  // u16[n_reads]: MarkBads' per-read sums (k_bad_sums), under DFK_F_MARK_BADS only
     uint64_t ck[DFK_CHECK_WORDS] = {};                // dfk_paths_digest: what the steps so far have left (ck[DFK_CK_VALID]: which)
     int64_t read_id0 = 0;                             // a rank of a sharded run: the whole set's number of its first read (dfk_paths_shard.inc)
     void* shard = nullptr; void (*shard_free)(void*) = nullptr;
@@ -45,7 +46,7 @@ void path_state_free(PathState* p) { delete p; }      // (its device blocks belo
 void paths_drop_results(dfk_ctx* c, PathState* P)
 {
     for (PathBatch& b : P->batches) { c->release(b.var); c->release(b.elem_off); }
-    c->release(P->digest);
+    c->release(P->digest); c->release(P->bad_sums);
     P->batches.clear(); P->built = false; P->n_reads = P->n_placed = P->n_edges = P->var_total = 0;
     for (uint64_t& w : P->ck) w = 0;
 }
@@ -156,6 +157,11 @@ int paths_build_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in)
                            in.pq, in.pq_off, in.pq_bytes, n, (uint32_t*)P->digest.p);
         HIP_TRY(hipGetLastError());
     }
+    // what MarkBads (10X/SecretOps.cc:71-109) will want of every read: asked for at dfk_create, since the reads are gone afterwards
+    const bool mark_bads = (c->cfg.flags & DFK_F_MARK_BADS) != 0;
+    if (mark_bads) { rc = c->alloc(P->bad_sums, std::max<uint64_t>(1, n) * 2, "bad-base sums"); if (rc) return rc; }
+    std::unique_ptr<Timer> bads_timer(mark_bads ? new Timer(c->stream) : nullptr);
+    float bads_ms = 0;                                                         // k_bad_sums alone, over the batches (dfk_stats.reserved[7])
     TRACE("paths: %.3f s in, tables checked, digests launched", wall_now() - t_in);
     // the filter in front of the index (dfk_paths_kernels.h): two bytes per k-mer, if the device has them to spare
     DevBuf filter;
@@ -236,8 +242,18 @@ int paths_build_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in)
                     if ((rc = c->alloc(B.var, std::max<uint64_t>(4, B.var_bytes), "a.paths data")) || (rc = c->alloc(B.elem_off, nb * 4, "a.paths offsets"))) return rc;
                     hipLaunchKernelGGL(k_path_emit, dim3(grid), dim3(256), 0, c->stream, (const uint64_t*)size_off.p, (const uint64_t*)slot_off.p, (const int32_t*)path.p,
                                        (const int32_t*)o_off.p, (const uint32_t*)o_len.p, (const uint32_t*)o_first.p, nb, (uint32_t*)B.var.p, (uint32_t*)B.elem_off.p);
+                    unsigned bflag = 0;
+                    if (mark_bads) {                                          // on the paths that stay: this attempt's, as k_path_emit left them
+                        bads_timer->start();
+                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bad_sums<K>), dim3(pgrid), dim3(256), 0, c->stream, pg, in.packed, in.packed_bytes, in.base_off, in.read_len,
+                                           in.pq, in.pq_off, (const uint32_t*)B.var.p, (const uint32_t*)B.elem_off.p, nb, r0, B.var_bytes,
+                                           (uint16_t*)P->bad_sums.p, (unsigned int*)((char*)ctr.p + 24));
+                        bads_ms += bads_timer->stop();
+                        HIP_TRY(hipMemcpyAsync(&bflag, (char*)ctr.p + 24, 4, hipMemcpyDeviceToHost, c->stream));
+                    }
                     HIP_TRY(hipGetLastError());
                     HIP_TRY(hipStreamSynchronize(c->stream));
+                    bad |= bflag;
                 }
                 c->release(parts); c->release(path); c->release(quals); c->release(o_off); c->release(o_len); c->release(o_first);
                 c->release(sizes); c->release(size_off); c->release(slot_off);
@@ -280,6 +296,7 @@ int paths_build_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in)
     }
     sink_guard.ok = true;
     c->st.reserved[3] = (uint64_t)(P->ms * 1000.0f);                           // microseconds spent pathing
+    if (mark_bads) c->st.reserved[7] = (uint64_t)(bads_ms * 1000.0f);          // ... of which in k_bad_sums
     TRACE("paths: %llu reads, %llu placed, %llu path edges, %zu batches, %.1f ms", (unsigned long long)n, (unsigned long long)P->n_placed,
           (unsigned long long)P->n_edges, P->batches.size(), P->ms);
     return 0;
@@ -306,7 +323,7 @@ int paths_build_any(dfk_ctx* c, const Inputs& in)
     if (rc) {
         (void)hipStreamSynchronize(c->stream);
         c->release_since(mark);
-        P->batches.clear(); P->built = false; P->digest = DevBuf{};
+        P->batches.clear(); P->built = false; P->digest = P->bad_sums = DevBuf{};
         if (!had_tables) { P->tables = false; P->xlat = P->he_ce = P->he_left = P->he_right = P->from_start = P->from_vtx = P->from_edge = P->to_start = P->to_vtx = P->to_edge = DevBuf{}; }
     }
     return rc;
@@ -816,6 +833,71 @@ PathState* built_paths(dfk_ctx* c)
     return (G->paths && G->paths->built) ? G->paths : nullptr;
 }
 
+// MarkBads (10X/SecretOps.cc:71-109): the paths that carry the per-read sums k_bad_sums gathered during the build, or
+// an error
+int bads_of(dfk_ctx* c, PathState** out)
+{
+    if (!c) return fail(DFK_E_ARG, "null context");
+    if (!(c->cfg.flags & DFK_F_MARK_BADS)) return fail(DFK_E_STATE, "no bad-base sums: the context was created without DFK_F_MARK_BADS");
+    PathState* P = built_paths(c);
+    if (!P || !P->bad_sums.p) return fail(DFK_E_STATE, "no bad-base sums: call dfk_paths_build (on a context created with DFK_F_MARK_BADS)");
+    *out = P;
+    return 0;
+}
+
+// a.bad (10X/DF.cc:604): the sums folded to a byte per pair, counted, digested and -- with a path -- written: whole
+// (part = false: "BINWRITE", the count, the bytes) or as this rank's bytes at pair first_pair of a file of total_pairs
+int bads_write(dfk_ctx* c, PathState* P, const char* path, bool part, uint64_t first_pair, uint64_t total_pairs, uint64_t first_read, uint64_t* n_marked, uint64_t* digest)
+{
+    const uint64_t n = P->n_reads, n_pairs = n / 2;
+    if (n % 2) return fail(DFK_E_ARG, "%llu reads: MarkBads works on pairs", (unsigned long long)n);
+    if (part && first_pair + n_pairs > total_pairs) return fail(DFK_E_ARG, "this rank's pairs do not fit the file described");
+    const unsigned cus = (unsigned)c->prop.multiProcessorCount;
+    const uint64_t mark = c->alloc_seq;
+    uint64_t hd[8] = {};
+    auto body = [&]() -> int {
+        DevBuf marks, dg;
+        int rc;
+        if ((rc = c->alloc(marks, std::max<uint64_t>(1, n_pairs), "bad-pair marks", Place::Low)) || (rc = c->alloc(dg, 64, "bad digest", Place::Low))) return rc;
+        HIP_TRY(hipMemsetAsync(dg.p, 0, 64, c->stream));
+        if (n_pairs) {
+            const unsigned grid = (unsigned)std::min<uint64_t>((n_pairs + 255) / 256, 32ull * cus);
+            hipLaunchKernelGGL(k_bad_marks, dim3(grid), dim3(256), 0, c->stream, (const uint16_t*)P->bad_sums.p, n_pairs, (uint8_t*)marks.p);
+            // over reads of h(whole-set read id, sum); the marks' plain sum is their number
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint16_t>), dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream,
+                               (const uint16_t*)P->bad_sums.p, n, 0x5555ull + first_read, (unsigned long long*)dg.p);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint8_t>), dim3(grid), dim3(256), 0, c->stream, (const uint8_t*)marks.p, n_pairs, 0x6666ull + first_pair, (unsigned long long*)dg.p + 4);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(hd, dg.p, 64, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (!path) return 0;
+        const int fd = open(path, part ? O_WRONLY | O_CREAT : O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        if (fd < 0) return fail(DFK_E_ARG, "cannot open %s", path);
+        const uint64_t in_file = part ? total_pairs : n_pairs;
+        if (!part || first_pair == 0) {                                   // BinaryWriter::writeFile of vec<Bool>, as for a.dup
+            struct { char magic[8]; uint64_t n; } h{{'B', 'I', 'N', 'W', 'R', 'I', 'T', 'E'}, in_file};
+            if (pwrite(fd, &h, 16, 0) != 16) rc = fail(DFK_E_ARG, "short write to %s", path);
+        }
+        if (!rc && part && ftruncate(fd, (off_t)(16 + in_file)) != 0) rc = fail(DFK_E_ARG, "cannot size %s", path);      // every rank: the same size
+        if (!rc) {
+            std::vector<FilePiece> pieces;
+            for (uint64_t o = 0; o < n_pairs; o += XFER_CHUNK) pieces.push_back(FilePiece{(const char*)marks.p + o, std::min<uint64_t>(XFER_CHUNK, n_pairs - o), 16 + first_pair + o});
+            if (write_pieces(c, fd, pieces)) rc = fail(DFK_E_ARG, "short write to %s", path);
+        }
+        if (close(fd) != 0 && !rc) rc = fail(DFK_E_ARG, "short write to %s", path);
+        return rc;
+    };
+    int rc;
+    try { rc = body(); } catch (const std::runtime_error& e) { rc = fail(DFK_E_HIP, "%s", e.what()); }
+    (void)hipStreamSynchronize(c->stream);
+    c->release_since(mark);
+    if (rc) return rc;
+    if (n_marked) *n_marked = hd[6];
+    if (digest) { digest[0] = hd[0]; digest[1] = hd[1]; }
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -1104,6 +1186,29 @@ int dfk_dups_write(dfk_ctx* c, const char* path, uint64_t* n_marked_pairs)
     release_path_lookup(c, graph_of(c));
     try { return dups_write(c, P, path ? path : "", n_marked_pairs); }
     catch (const std::runtime_error& e) { return fail(DFK_E_HIP, "%s", e.what()); }
+    });
+}
+
+int dfk_bads_sums(dfk_ctx* c, uint16_t* out, uint64_t cap)
+{
+    return guarded([&]() -> int {
+    PathState* P = nullptr;
+    if (int rc = bads_of(c, &P)) return rc;
+    if (!out && P->n_reads) return fail(DFK_E_ARG, "null argument");
+    if (cap < P->n_reads) return fail(DFK_E_ARG, "buffer too small: %llu < %llu reads", (unsigned long long)cap, (unsigned long long)P->n_reads);
+    HIP_TRY(hipSetDevice(c->device));
+    if (P->n_reads) HIP_TRY(hipMemcpy(out, P->bad_sums.p, P->n_reads * 2, hipMemcpyDeviceToHost));
+    return 0;
+    });
+}
+
+int dfk_bads_write(dfk_ctx* c, const char* path, uint64_t* n_marked_pairs, uint64_t* digest)
+{
+    return guarded([&]() -> int {
+    PathState* P = nullptr;
+    if (int rc = bads_of(c, &P)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return bads_write(c, P, path, false, 0, P->n_reads / 2, (uint64_t)P->read_id0, n_marked_pairs, digest);
     });
 }
 

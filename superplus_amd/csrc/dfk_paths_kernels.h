@@ -573,6 +573,111 @@ k_path_emit(const uint64_t* __restrict__ size_off, const uint64_t* __restrict__ 
     }
 }
 
+// ============================================================================ MarkBads (10X/SecretOps.cc:71-109), gathered while the reads are here
+// Per placed read the summed qualities of the bases that disagree with the concatenation of its path's edges (hb.Cat: the
+// first edge whole, every later one from its base K-1 on), over the positions where the WHOLE read lies on that sequence;
+// saturated at 65535, 0 for a read without a path.  dfk_bads_write folds the sums to a byte per pair (sum > 150).
+//
+// ONE LANE PER READ, not a wave: a read of 100-150 bases is seven to ten steps of sixteen bases, so a wave per read would
+// leave 54 of its 64 lanes without work, and the per-read state (the place on the path, the cursor into the PQVec
+// stream) is scalar.  The lanes of a wave hold neighbouring reads -- their base words are 25-38 bytes apart and share
+// cache lines -- and diverge only where a read has a mismatch: the XOR of sixteen bases is zero for nearly every step, the
+// qualities are touched only at the positions that differ, and their PQVec blocks are walked forwards once (mismatches
+// come in rising read position), a constant block giving its minQ without a look at its payload.  Bound by the latency of the
+// edge gather (path entry -> he_ce -> edge record -> edge bases), like k_path_reads, which takes nine times as long.
+// Resource report (make asm, resusage.py; gfx950): K = 40, 48 and 60 alike 52 VGPRs, no AGPRs, 103 SGPRs, no scratch, no LDS,
+// occupancy 7 waves per SIMD (k_path_reads beside it: 85 VGPRs, occupancy 5).
+struct QualCursor {                                       // the PQVec block that holds read position pos0 .. pos0 + nQs - 1
+    uint64_t p, end; uint32_t pos0, nQs, nBits, minQ; bool ok;
+    __device__ __forceinline__ void load(const uint8_t* __restrict__ pq)
+    {
+        nQs = 0; ok = false;
+        if (p + 3 > end) return;
+        nQs = pq[p];
+        const uint32_t hdr = pq[p + 1] | ((uint32_t)pq[p + 2] << 8);
+        nBits = hdr & 7u; minQ = (hdr >> 3) & 63u;
+        ok = nQs != 0 && p + (((uint64_t)nQs * nBits + 24) >> 3) <= end;
+    }
+    // the quality at read position pos (>= every position asked for before); false if the stream does not reach it
+    __device__ __forceinline__ bool at(const uint8_t* __restrict__ pq, uint32_t pos, uint32_t* q)
+    {
+        while (ok && pos >= pos0 + nQs) { p += ((uint64_t)nQs * nBits + 24) >> 3; pos0 += nQs; load(pq); }
+        if (!ok) return false;
+        uint32_t v = 0;
+        if (nBits) {
+            const uint64_t bit = 8 * (p + 1) + 9 + (uint64_t)(pos - pos0) * nBits, by = bit >> 3, blk_end = p + (((uint64_t)nQs * nBits + 24) >> 3);
+            const uint32_t w = pq[by] | (by + 1 < blk_end ? (uint32_t)pq[by + 1] << 8 : 0u);    // (a field of <= 7 bits spans at most two bytes)
+            v = (w >> (bit & 7)) & ((1u << nBits) - 1u);
+        }
+        *q = minQ + v;
+        return true;
+    }
+};
+
+template <int K>
+__global__ void __launch_bounds__(256)
+k_bad_sums(PathGraph G, const uint8_t* __restrict__ packed, uint64_t packed_bytes, const uint64_t* __restrict__ base_off, const uint32_t* __restrict__ read_len,
+           const uint8_t* __restrict__ pq, const uint64_t* __restrict__ pq_off, const uint32_t* __restrict__ var, const uint32_t* __restrict__ elem_off,
+           uint64_t nb, uint64_t r0, uint64_t var_bytes, uint16_t* __restrict__ sums /* [n_reads] */, unsigned int* __restrict__ bad)
+{
+    const uint32_t* rwords = reinterpret_cast<const uint32_t*>(packed);
+    const uint32_t* ewords = reinterpret_cast<const uint32_t*>(G.store);
+    const uint64_t r_nwords = (packed_bytes + 3) >> 2;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < nb; i += (uint64_t)gridDim.x * 256) {
+        const uint64_t r = r0 + i, w0 = elem_off[i] >> 2, w1 = (i + 1 < nb ? (uint64_t)elem_off[i + 1] : var_bytes) >> 2;
+        uint32_t sum = 0;
+        if (w1 - w0 > 2) {
+            const int64_t off = (int32_t)var[w0], L = (int64_t)read_len[r];
+            const uint64_t r_byte0 = base_off[r];
+            QualCursor qc{pq_off[r], pq_off[r + 1], 0, 0, 0, 0, false};
+            bool q_open = false;
+            int64_t seg0 = 0;                                              // where on the concatenation the current edge's share starts
+            for (uint64_t w = w0 + 2; w < w1 && seg0 - off < L; ++w) {
+                const uint32_t x = G.he_ce[var[w]];
+                const EdgeRec er = G.ce[x >> 1];
+                const bool rc = (x & 1u) != 0u;
+                const int64_t Le = (int64_t)er.n + K - 1, skip = w == w0 + 2 ? 0 : K - 1, seg1 = seg0 + Le - skip;
+                // read positions [la, lb) lie on this edge's share: inside the read, inside the share
+                const int64_t la = seg0 - off > 0 ? seg0 - off : 0, lb = seg1 - off < L ? seg1 - off : L;
+                for (int64_t l = la; l < lb; l += 16) {
+                    const uint32_t cnt = lb - l < 16 ? (uint32_t)(lb - l) : 16u;
+                    const int64_t j = l + off - seg0 + skip;               // index on the edge as the path runs along it: j + cnt <= Le
+                    uint32_t e;
+                    if (!rc) e = bases16(ewords, G.store_words, er.byte_off, (uint64_t)j);
+                    else {
+                        // positions j .. j+15 against the orientation are stored positions Le-1-j down to Le-16-j; near the stored
+                        // start (s < 0) the sixteen from 0 are taken and the fields that do not exist shifted out
+                        const int64_t s = Le - 16 - j;
+                        e = rev2_32(~bases16(ewords, G.store_words, er.byte_off, (uint64_t)(s > 0 ? s : 0)));
+                        if (s < 0) e >>= 2 * (uint32_t)(-s);
+                    }
+                    const uint32_t d = bases16(rwords, r_nwords, r_byte0, (uint64_t)l) ^ e;
+                    uint32_t mm = (d | (d >> 1)) & 0x55555555u;             // one bit per base that differs
+                    if (cnt < 16u) mm &= (1u << (2 * cnt)) - 1u;
+                    while (mm) {
+                        const uint32_t pos = (uint32_t)l + ((uint32_t)__builtin_ctz(mm) >> 1);
+                        mm &= mm - 1u;
+                        if (!q_open) { q_open = true; qc.load(pq); }
+                        uint32_t q = 0;
+                        if (!qc.at(pq, pos, &q)) { atomicOr(bad, 16u); mm = 0; }
+                        sum += q;
+                    }
+                }
+                seg0 = seg1;
+            }
+        }
+        sums[r] = (uint16_t)(sum < 65535u ? sum : 65535u);
+    }
+}
+
+// a.bad: a byte per pair, set when the sum of either of its reads is above MAX_BAD_SUM = 150 (SecretOps.cc:78,107)
+__global__ void __launch_bounds__(256)
+k_bad_marks(const uint16_t* __restrict__ sums, uint64_t n_pairs, uint8_t* __restrict__ marks)
+{
+    for (uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < n_pairs; p += (uint64_t)gridDim.x * 256)
+        marks[p] = (sums[2 * p] > 150u || sums[2 * p + 1] > 150u) ? 1 : 0;
+}
+
 // ============================================================================ row f-4: paths index, duplicate marks
 // What MarkDups needs of a read besides its path, gathered while the reads are at hand (dfk_paths_build): the first five
 // bases as a base-4 number (10X/SecretOps.cc:430-433) in bits 0-9, the sum of its qualities (:474-481) above them.

@@ -412,4 +412,14 @@ int dfk_shard_dup_write(dfk_ctx* c, const void* d_ans_back, uint64_t n, const ch
     });
 }
 
+int dfk_bads_write_part(dfk_ctx* c, const char* path, uint64_t first_pair, uint64_t total_pairs, uint64_t* n_marked, uint64_t* digest)
+{
+    return guarded([&]() -> int {
+    PathState* P = nullptr;
+    if (int rc = bads_of(c, &P)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return bads_write(c, P, path, true, first_pair, total_pairs, 2 * first_pair, n_marked, digest);
+    });
+}
+
 } // extern "C"

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("DFK_LIB") or os.path.join(_HERE, "libdfk.so")      # 
 ABI_VERSION = 1
 F_KEEP_PRE_ADJ = 1
 F_KEEP_INPUTS = 2
+F_MARK_BADS = 4
 
 ENTRY_DTYPE = np.dtype([("w0", "<u8"), ("w1", "<u8"), ("edge_id", "<u4"), ("count_ctx", "<u4"),
                         ("bc", "<i4"), ("pad", "<u4")])
@@ -29,6 +30,7 @@ EXPORTS = [
     "dfk_paths_build", "dfk_paths_build_device", "dfk_paths_stats", "dfk_paths_write", "dfk_paths_fetch", "dfk_paths_index_write", "dfk_dups_write", "dfk_paths_index_dups_write",
     "dfk_paths_digest", "dfk_paths_verify", "dfk_paths_verify_device", "dfk_pbf_run", "dfk_pbf_result", "dfk_pbf_free",
     "dfk_paths_var_bytes", "dfk_paths_write_part", "dfk_shard_pidx_pairs", "dfk_shard_pidx_write", "dfk_shard_dup_keys", "dfk_shard_dup_answer", "dfk_shard_dup_write",
+    "dfk_bads_sums", "dfk_bads_write", "dfk_bads_write_part",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -68,6 +70,7 @@ class Stats(C.Structure):
         d["gate_timeouts"] = int(self.reserved[4])
         d["hbm_held"] = int(self.reserved[5])
         d["n_scan_launches"] = int(self.reserved[6])
+        d["us_bad_sums"] = int(self.reserved[7])
         return d
 
 
@@ -105,10 +108,11 @@ class Dfk:
     torch tensors already on this context's device."""
 
     def __init__(self, K=48, min_qual=7, min_freq=3, min_bc=2, ign_bc_below=0, device=0, hbm_budget_bytes=0,
-                 minimizer_len=0, keep_pre_adjacency=False, inst_per_item=0, passes=0, keep_inputs=False):
+                 minimizer_len=0, keep_pre_adjacency=False, inst_per_item=0, passes=0, keep_inputs=False, mark_bads=False):
         cfg = Config(abi_version=ABI_VERSION, K=K, min_qual=min_qual, min_freq=min_freq, min_bc=min_bc, device=device,
                      ign_bc_below=ign_bc_below, hbm_budget_bytes=hbm_budget_bytes, minimizer_len=minimizer_len,
-                     flags=(F_KEEP_PRE_ADJ if keep_pre_adjacency else 0) | (F_KEEP_INPUTS if keep_inputs else 0), inst_per_item=inst_per_item)
+                     flags=(F_KEEP_PRE_ADJ if keep_pre_adjacency else 0) | (F_KEEP_INPUTS if keep_inputs else 0) | (F_MARK_BADS if mark_bads else 0),
+                     inst_per_item=inst_per_item)
         cfg.reserved[0] = passes          # forced number of bucket-range passes; 0 = sized from the free HBM
         self._ctx = C.c_void_p()
         _check(lib().dfk_create(C.byref(cfg), C.byref(self._ctx)))
@@ -272,6 +276,20 @@ class Dfk:
         n = C.c_uint64()
         _check(lib().dfk_paths_index_dups_write(self._ctx, None if directory is None else directory.encode(), None if path is None else path.encode(), C.byref(n)))
         return n.value
+
+    def bads_sums(self):
+        """dfk_bads_sums: MarkBads' per-read sums, u16[n_reads] (mark_bads=True; saturated at 65535, 0 = unplaced or no mismatch)."""
+        a = C.c_uint64()
+        n = a.value if lib().dfk_paths_stats(self._ctx, C.byref(a), None, None) == 0 else 0      # (no paths: dfk_bads_sums says what is missing)
+        out = np.zeros(n, np.uint16)
+        _check(lib().dfk_bads_sums(self._ctx, _p(out), C.c_uint64(n)))
+        return out
+
+    def bads_write(self, path):
+        """a.bad (MarkBads); returns (pairs marked, (sum, xor) digest of the per-read sums).  None = no file."""
+        n = C.c_uint64(); dg = (C.c_uint64 * 2)()
+        _check(lib().dfk_bads_write(self._ctx, None if path is None else path.encode(), C.byref(n), dg))
+        return n.value, (int(dg[0]), int(dg[1]))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
