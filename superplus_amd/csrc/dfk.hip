@@ -21,6 +21,7 @@
 #include <condition_variable>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <thread>
 #include <vector>
 
@@ -64,6 +65,7 @@ void dev_give(void* p) { (void)hipFree(p); }
 
 bool g_trace = getenv("DFK_TRACE") != nullptr;
 #define TRACE(...) do { if (g_trace) { fprintf(stderr, "[dfk] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
+inline uint32_t env_u32(const char* name, uint32_t dflt) { const char* e = getenv(name); return e ? (uint32_t)atoi(e) : dflt; }
 inline double wall_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // LDS table geometry per K (DESIGN.md "count kernel"): slots and waves per workgroup
@@ -206,8 +208,6 @@ struct Timer {
     void start() { (void)hipEventRecord(a, s); }
     float stop() { (void)hipEventRecord(b, s); (void)hipEventSynchronize(b); float ms = 0; (void)hipEventElapsedTime(&ms, a, b); return ms; }
 };
-
-uint32_t ceil_log2(uint64_t v) { uint32_t b = 0; while ((1ull << b) < v) ++b; return b; }
 
 // ------------------------------------------------------------------ stage: trim (a1)
 template <int K>
@@ -842,50 +842,36 @@ int launch_count(dfk_ctx* c, const Partition& P, const ItemRange* d_items, uint6
     return 0;
 }
 
+// table[b1] - table[b0] of every range, for each of the device tables of prefix sums given (one upload of the ranges)
+int gather_diffs(dfk_ctx* c, const std::vector<ItemRange>& ranges, std::initializer_list<std::pair<const DevBuf*, std::vector<uint64_t>*>> tables)
+{
+    const uint32_t n = (uint32_t)ranges.size();
+    DevBuf d_idx, d_val;
+    int rc = c->alloc(d_idx, 8ull * n, "gather index"); if (!rc) rc = c->alloc(d_val, 16ull * n, "gather values"); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d_idx.p, ranges.data(), 8ull * n, hipMemcpyHostToDevice, c->stream));   // (b0, b1: the indices as they lie)
+    std::vector<uint64_t> val(2 * n);
+    for (const auto& t : tables) {
+        hipLaunchKernelGGL(k_gather_u64, dim3((2 * n + 255) / 256), dim3(256), 0, c->stream, (const uint64_t*)t.first->p, (const uint32_t*)d_idx.p, 2 * n, (uint64_t*)d_val.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(val.data(), d_val.p, 16ull * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (uint32_t i = 0; i < n; ++i) t.second->push_back(val[2 * i + 1] - val[2 * i]);
+    }
+    c->release(d_idx); c->release(d_val);
+    return 0;
+}
+
 template <int K, int NBC>
 int launch_count_big(dfk_ctx* c, const Partition& P, const std::vector<ItemRange>& singles, CountRun& R)
 {
     constexpr int KW = KTraits<K>::KW, NW = 8;
-    // instance counts of the single buckets (ipre[b1] - ipre[b0]) size their tables: >= 2x the instances,
-    // an upper bound on the distinct k-mers
+    // instance counts of the single buckets size their tables, record counts their chunk tickets
     const uint32_t n = (uint32_t)singles.size();
-    std::vector<uint32_t> idx(2 * n);
-    for (uint32_t i = 0; i < n; ++i) { idx[2 * i] = singles[i].b0; idx[2 * i + 1] = singles[i].b1; }
-    DevBuf d_idx, d_val;
-    int rc = c->alloc(d_idx, 8ull * n, "gather index"); if (rc) return rc;
-    rc = c->alloc(d_val, 16ull * n, "gather values"); if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(d_idx.p, idx.data(), 8ull * n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_gather_u64, dim3((2 * n + 255) / 256), dim3(256), 0, c->stream, (const uint64_t*)P.ipre.p,
-                       (const uint32_t*)d_idx.p, 2 * n, (uint64_t*)d_val.p);
-    HIP_TRY(hipGetLastError());
-    std::vector<uint64_t> val(2 * n);
-    HIP_TRY(hipMemcpyAsync(val.data(), d_val.p, 16ull * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->release(d_idx); c->release(d_val);
-    std::vector<BigItem> items; uint64_t words = 0, tot_inst = 0;
-    std::vector<uint64_t> chunk_pre(n + 1, 0), slot_pre(n + 1, 0), rec(2 * n);
-    // record ranges of the items (for the chunk tickets)
-    {
-        DevBuf d_i2, d_v2;
-        rc = c->alloc(d_i2, 8ull * n, "gather index"); if (rc) return rc;
-        rc = c->alloc(d_v2, 16ull * n, "gather values"); if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(d_i2.p, idx.data(), 8ull * n, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_gather_u64, dim3((2 * n + 255) / 256), dim3(256), 0, c->stream, (const uint64_t*)P.base.p,
-                           (const uint32_t*)d_i2.p, 2 * n, (uint64_t*)d_v2.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(rec.data(), d_v2.p, 16ull * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->release(d_i2); c->release(d_v2);
-    }
-    for (uint32_t i = 0; i < n; ++i) {
-        tot_inst += val[2 * i + 1] - val[2 * i];
-        chunk_pre[i + 1] = chunk_pre[i] + (rec[2 * i + 1] - rec[2 * i] + COUNT_CHUNK - 1) / COUNT_CHUNK;
-    }
-    // A table is sized for the distinct k-mers its bucket is expected to hold -- instances x (distinct k-mers per
-    // instance seen so far, with a margin) -- at load <= 0.5; 2 x instances is the certain bound and costs 56 bytes
-    // per instance (42 GB for the hot buckets of one pass of a human-scale set with a 10 % repeat family).  An insert
-    // that runs out of probe steps says the guess was too low: every table is then rebuilt twice as large.
-    double per_inst = c->distinct_per_inst > 0.0 ? std::min(1.0, std::max(0.05, 1.5 * c->distinct_per_inst)) : 1.0;
+    std::vector<uint64_t> inst, rec;
+    int rc = gather_diffs(c, singles, {{&P.ipre, &inst}, {&P.base, &rec}}); if (rc) return rc;
+    const uint64_t tot_inst = std::accumulate(inst.begin(), inst.end(), (uint64_t)0);
+    const std::vector<uint64_t> chunk_pre = chunk_prefixes(rec);
+    double per_inst = table_distinct_per_inst(c->distinct_per_inst);
     DevBuf d_items, d_fail, d_pre;
     {
         // the fallback's own output buffer; a pass can come here more than once (the sub-buckets of split hot buckets,
@@ -910,28 +896,18 @@ int launch_count_big(dfk_ctx* c, const Partition& P, const std::vector<ItemRange
     CountParams cpb = R.cp; cpb.seg_cap = R.big_cap;                       // the fallback writes to its own buffer
     const unsigned cus = (unsigned)c->prop.multiProcessorCount;
     for (;;) {
-        items.clear(); words = 0;
-        bool certain = true;
-        for (uint32_t i = 0; i < n; ++i) {
-            const uint64_t inst = val[2 * i + 1] - val[2 * i];
-            const uint64_t guess = std::min<uint64_t>(inst, (uint64_t)((double)inst * per_inst) + 256);
-            certain = certain && guess == inst;
-            const uint32_t l2 = std::max<uint32_t>(13, ceil_log2(2 * guess + 64));
-            items.push_back(BigItem{singles[i].b0, singles[i].b1, words, l2, 0});
-            words += (uint64_t)(KW + 4 + (NBC > 1 ? NBC - 1 : 0)) << l2;   // keys, state, contexts, counts, barcode words (BigView)
-            slot_pre[i + 1] = slot_pre[i] + (1ull << l2);
-        }
+        const BigTables T = size_big_tables(singles, inst, per_inst, big_slot_words(KW, NBC));
         DevBuf pool;
-        rc = c->alloc(pool, words * 4 + 8, "HBM fallback tables"); if (rc) return rc;
+        rc = c->alloc(pool, T.words * 4 + 8, "HBM fallback tables"); if (rc) return rc;
         // (zeroed by our own grid-stride kernel: the pool of a pass with a 10^8-instance bucket is past 4 GiB)
-        hipLaunchKernelGGL(k_fill_u64, dim3(4096), dim3(256), 0, c->stream, (uint64_t*)pool.p, words / 2 + (words & 1), 0ull);
+        hipLaunchKernelGGL(k_fill_u64, dim3(4096), dim3(256), 0, c->stream, (uint64_t*)pool.p, T.words / 2 + (T.words & 1), 0ull);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemsetAsync(d_fail.p, 0, 16, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_items.p, items.data(), items.size() * sizeof(BigItem), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_slot_pre, slot_pre.data(), 8ull * (n + 1), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_items.p, T.items.data(), T.items.size() * sizeof(BigItem), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_slot_pre, T.slot_pre.data(), 8ull * (n + 1), hipMemcpyHostToDevice, c->stream));
         // the whole grid works on the fallback tables together (d_fail + 8: the chunk ticket)
         const unsigned g_ins = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((chunk_pre[n] + NW * BIG_TICKET_CHUNKS - 1) / (NW * BIG_TICKET_CHUNKS), 4ull * cus));
-        const unsigned g_slot = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((slot_pre[n] + 255) / 256, 16ull * cus));
+        const unsigned g_slot = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((T.slot_pre[n] + 255) / 256, 16ull * cus));
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_big_insert<K, NW, NBC>), dim3(g_ins), dim3(NW * 64), 0, c->stream,
                            (const uint4*)P.records.p, (const BigItem*)d_items.p, (const uint64_t*)P.base.p, (const uint64_t*)d_chunk_pre, n,
                            (uint32_t*)pool.p, (unsigned long long*)d_fail.p + 1, (uint32_t*)d_fail.p);
@@ -945,13 +921,13 @@ int launch_count_big(dfk_ctx* c, const Partition& P, const std::vector<ItemRange
             const unsigned int zero[4] = {};
             (void)hipMemcpyToSymbol(HIP_SYMBOL(g_big_fail), zero, sizeof zero);
             c->release(pool);
-            if (certain) {
+            if (T.certain) {
                 c->release(d_items); c->release(d_fail); c->release(d_pre);
                 return fail(DFK_E_HIP, "an insert into an HBM fallback table gave up after %u probe steps and %u waits on a locked slot "
                                        "(table of 2^%u slots at load <= 0.5; %u tables, %llu instances in this pass's fallback)", info[1], info[2], info[3], n,
                             (unsigned long long)tot_inst);
             }
-            per_inst = std::min(1.0, 2.0 * per_inst);
+            per_inst = table_retry_per_inst(per_inst);
             TRACE("fallback: an HBM table filled up (2^%u slots): rebuilding the tables for %.2f distinct k-mers per instance", info[3], per_inst);
             continue;
         }
@@ -971,21 +947,38 @@ int launch_count_big(dfk_ctx* c, const Partition& P, const std::vector<ItemRange
     return 0;
 }
 
+// Items that overflowed their LDS table are halved by bucket index and counted again until only single fine buckets
+// are left of them, which go to `singles`.
+template <int K, int NBC>
+int count_halved(dfk_ctx* c, const Partition& P, const CountRun& R, bool single_kmer_records, std::vector<ItemRange>& overflowed, std::vector<ItemRange>* singles)
+{
+    while (!overflowed.empty()) {
+        const std::vector<ItemRange> next = halve_items(overflowed, singles);
+        overflowed.clear();
+        if (next.empty()) break;
+        if (!single_kmer_records) TRACE("retrying %zu split items", next.size());
+        DevBuf d_next; float ignored = 0;
+        int rc = c->alloc(d_next, next.size() * sizeof(ItemRange), "split items"); if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(d_next.p, next.data(), next.size() * sizeof(ItemRange), hipMemcpyHostToDevice, c->stream));
+        rc = launch_count<K, NBC>(c, P, (const ItemRange*)d_next.p, next.size(), R, &overflowed, &ignored, nullptr, single_kmer_records);
+        c->release(d_next); if (rc) return rc;
+    }
+    return 0;
+}
+
 // Fine buckets too rich for one LDS table, the linear way: one pass over their records writes every instance out as
 // a record of one k-mer, grouped by a second hash of the canonical k-mer into sub-buckets of ~700 distinct k-mers
 // (k_hot_split: count, scan, scatter); the sub-buckets are then an ordinary small pass for k_count.  What still does
 // not fit (a guess too low) goes to the HBM tables.  Returns DFK_E_NOMEM untouched when the expanded records do not
 // fit: the caller then falls back to sub-passes.
 template <int K, int NBC>
-int count_split(dfk_ctx* c, const Partition& P, const std::vector<ItemRange>& buckets, const std::vector<uint64_t>& inst,
-                const std::vector<uint32_t>& log2p, CountRun& R)
+int count_split(dfk_ctx* c, const Partition& P, const std::vector<ItemRange>& hot, const std::vector<uint64_t>& inst, const SplitCandidates& sp, size_t i0, size_t i1, CountRun& R)   // candidates [i0, i1) of the single buckets `hot`
 {
     constexpr int NW = 8;
-    const uint32_t n = (uint32_t)buckets.size();
-    std::vector<HotItem> items(n);
-    std::vector<uint32_t> idx(2 * n);
+    const uint32_t n = (uint32_t)(i1 - i0);
+    std::vector<HotItem> items(n); std::vector<ItemRange> buckets(n);
     uint64_t ns = 0, tot = 0;
-    for (uint32_t i = 0; i < n; ++i) { items[i] = HotItem{buckets[i].b0, buckets[i].b1, (uint32_t)ns, log2p[i]}; ns += 1ull << log2p[i]; tot += inst[i]; idx[2 * i] = buckets[i].b0; idx[2 * i + 1] = buckets[i].b1; }
+    for (uint32_t i = 0; i < n; ++i) { buckets[i] = hot[sp.at[i0 + i]]; items[i] = HotItem{buckets[i].b0, buckets[i].b1, (uint32_t)ns, sp.log2p[i0 + i]}; ns += 1ull << sp.log2p[i0 + i]; tot += inst[sp.at[i0 + i]]; }
     if (ns >= (1ull << 24)) { fail(DFK_E_NOMEM, "more than 2^24 sub-buckets in one pass"); return E_SPLIT_NO_ROOM; }   // (the record header keeps 24 bits)
     const uint64_t mark = c->alloc_seq;
     bool started = false;             // once a sub-bucket has been counted there is no way back to sub-passes: an error undoes the pass
@@ -995,16 +988,9 @@ int count_split(dfk_ctx* c, const Partition& P, const std::vector<ItemRange>& bu
         return rc;
     };
     // record ranges of the buckets -> chunk tickets
-    DevBuf d_idx, d_val, d_items, d_pre, d_tk, acc;
-    int rc = c->alloc(d_idx, 8ull * n, "gather index"); if (rc) return undo(rc);
-    rc = c->alloc(d_val, 16ull * n, "gather values"); if (rc) return undo(rc);
-    HIP_TRY(hipMemcpyAsync(d_idx.p, idx.data(), 8ull * n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_gather_u64, dim3((2 * n + 255) / 256), dim3(256), 0, c->stream, (const uint64_t*)P.base.p, (const uint32_t*)d_idx.p, 2 * n, (uint64_t*)d_val.p);
-    HIP_TRY(hipGetLastError());
-    std::vector<uint64_t> rec(2 * n), chunk_pre(n + 1, 0);
-    HIP_TRY(hipMemcpyAsync(rec.data(), d_val.p, 16ull * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < n; ++i) chunk_pre[i + 1] = chunk_pre[i] + (rec[2 * i + 1] - rec[2 * i] + COUNT_CHUNK - 1) / COUNT_CHUNK;
+    DevBuf d_items, d_pre, d_tk, acc; std::vector<uint64_t> rec;
+    int rc = gather_diffs(c, buckets, {{&P.base, &rec}}); if (rc) return undo(rc);
+    const std::vector<uint64_t> chunk_pre = chunk_prefixes(rec);
     rc = c->alloc(d_items, (uint64_t)n * sizeof(HotItem), "hot buckets"); if (rc) return undo(rc);
     rc = c->alloc(d_pre, 8ull * (n + 1), "hot bucket chunks"); if (rc) return undo(rc);
     rc = c->alloc(d_tk, 16, "hot bucket ticket"); if (rc) return undo(rc);
@@ -1048,20 +1034,7 @@ int count_split(dfk_ctx* c, const Partition& P, const std::vector<ItemRange>& bu
     std::vector<ItemRange> overflowed, singles;
     float ignored = 0;
     rc = launch_count<K, NBC>(c, P2, (const ItemRange*)P2.items.p, P2.n_items, R, &overflowed, &ignored, nullptr, true); if (rc) return undo(rc);
-    while (!overflowed.empty()) {
-        std::vector<ItemRange> next;
-        for (const ItemRange& r : overflowed) {
-            if (r.b1 - r.b0 <= 1) { singles.push_back(r); continue; }
-            const uint32_t mid = r.b0 + (r.b1 - r.b0) / 2;
-            next.push_back({r.b0, mid}); next.push_back({mid, r.b1});
-        }
-        overflowed.clear();
-        if (next.empty()) break;
-        DevBuf d_next; rc = c->alloc(d_next, next.size() * sizeof(ItemRange), "split items"); if (rc) return undo(rc);
-        HIP_TRY(hipMemcpyAsync(d_next.p, next.data(), next.size() * sizeof(ItemRange), hipMemcpyHostToDevice, c->stream));
-        rc = launch_count<K, NBC>(c, P2, (const ItemRange*)d_next.p, next.size(), R, &overflowed, &ignored, nullptr, true);
-        if (rc) return undo(rc);
-    }
+    rc = count_halved<K, NBC>(c, P2, R, true, overflowed, &singles); if (rc) return undo(rc);
     TRACE("fallback: %u buckets (%llu instances) split into %llu sub-buckets, %llu items; %zu sub-buckets to HBM tables", n, (unsigned long long)tot,
           (unsigned long long)ns, (unsigned long long)P2.n_items, singles.size());
     if (!singles.empty()) { rc = launch_count_big<K, NBC>(c, P2, singles, R); if (rc) return undo(rc); }
@@ -1071,8 +1044,6 @@ int count_split(dfk_ctx* c, const Partition& P, const std::vector<ItemRange>& bu
     return 0;
 }
 
-// Count one pass: run k_count over its items (+ split / HBM-table fallbacks), gather the pass's solid
-// k-mers into a dense part.
 // barcodes a table slot remembers: max(1, MIN_BC - 1); 0 without barcodes
 int barcode_words(const dfk_ctx* c, bool have_bc)
 { return !have_bc ? 0 : (int)std::max<uint32_t>(1, std::min<uint32_t>(c->cfg.min_bc, DFK_MAX_MIN_BC) - (c->cfg.min_bc > 1 ? 1 : 0)); }
@@ -1085,7 +1056,7 @@ int count_prepare(dfk_ctx* c, const Partition& P, CountRun& R, int nbc)
     const unsigned attempt = c->seg_attempt;
     // Output: the pass's part of the dictionary, reserved now (from the bottom of the arena's free room, where the
     // dictionary grows) so that what is placed next -- the block of the following range -- cannot fragment the
-    // room it needs.  The persistent workgroups fill it chunk by chunk (WgOut); count_run cuts it to size.
+    // room it needs.  The persistent workgroups fill it chunk by chunk (WgOut); finish_part cuts it to size.
     // Every solid k-mer has >= min_freq instances, which bounds the total; after the first pass the observed
     // solid/instance ratio holds to a fraction of a percent (buckets are hash-distributed).
     R.grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(P.n_items, count_grid<K>(c, nbc)));
@@ -1106,176 +1077,24 @@ int count_prepare(dfk_ctx* c, const Partition& P, CountRun& R, int nbc)
     return 0;
 }
 
-template <int K, int NBC>
-int count_run(dfk_ctx* c, const Partition& P, CountRun& R)
+// Cut a counted pass's reservation to size: entries from its tail fill the holes the persistent workgroups left, the
+// HBM tables' output goes behind, and the dense part joins the dictionary.
+template <int K>
+int finish_part(dfk_ctx* c, const Partition& P, CountRun& R)
 {
-    int rc = 0;
-    Timer t(c->stream);
-    std::vector<ItemRange> overflowed;
-    c->st.n_items += P.n_items;
-    const float ms_before = c->st.ms_count;
-    rc = launch_count<K, NBC>(c, P, (const ItemRange*)P.items.p, P.n_items, R, &overflowed, &c->st.ms_count); if (rc) return rc;
-    if (g_trace) {
-        unsigned int gate[2] = {0, 0};
-        (void)hipMemcpy(gate, c->d_resident, 8, hipMemcpyDeviceToHost);
-        TRACE("k_count: %llu instances in %.1f ms (%.1f G instances/s), reservation %.2f GB, %u of %u workgroups idle, %u gate timeouts so far",
-              (unsigned long long)P.n_inst, c->st.ms_count - ms_before, 1e-6 * (double)P.n_inst / (double)(c->st.ms_count - ms_before), R.d_part.bytes / 1e9,
-              c->last_wg_idle, R.grid, gate[1]);
-    }
-    t.start();
-    // items that overflowed their LDS table are halved by bucket index and retried; a single fine bucket
-    // that still overflows is counted in an HBM table
-    c->st.n_overflow_items += overflowed.size();
-    std::vector<ItemRange> singles;
-    while (!overflowed.empty()) {
-        std::vector<ItemRange> next;
-        for (const ItemRange& r : overflowed) {
-            if (r.b1 - r.b0 <= 1) { singles.push_back(r); continue; }
-            const uint32_t mid = r.b0 + (r.b1 - r.b0) / 2;
-            next.push_back({r.b0, mid}); next.push_back({mid, r.b1});
-        }
-        overflowed.clear();
-        if (next.empty()) break;
-        TRACE("retrying %zu split items", next.size());
-        DevBuf d_next; rc = c->alloc(d_next, next.size() * sizeof(ItemRange), "split items"); if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(d_next.p, next.data(), next.size() * sizeof(ItemRange), hipMemcpyHostToDevice, c->stream));
-        float ignored = 0;
-        rc = launch_count<K, NBC>(c, P, (const ItemRange*)d_next.p, next.size(), R, &overflowed, &ignored);
-        c->release(d_next);
-        if (rc) return rc;
-    }
-    TRACE("fallback: %zu single-bucket items", singles.size());
-    if (!singles.empty()) {
-        // A fine bucket too rich for one LDS table is counted in 2^p sub-passes of k_count, each taking the k-mers
-        // of one selector value (all instances of a k-mer share it, so solidity and counts are exact; neighbours in
-        // another sub-pass are settled with the other cross-item bits).  p from the bucket's instance count, which
-        // bounds its distinct k-mers: 1024 per sub-pass at most, in a 2048-slot table that gives up at 1536.
-        // Buckets beyond 64 sub-passes (a minimizer owning a sizeable share of the genome) get an HBM table.
-        const uint32_t n = (uint32_t)singles.size();
-        std::vector<uint32_t> idx(2 * n);
-        for (uint32_t i = 0; i < n; ++i) { idx[2 * i] = singles[i].b0; idx[2 * i + 1] = singles[i].b1; }
-        DevBuf d_idx, d_val;
-        rc = c->alloc(d_idx, 8ull * n, "gather index"); if (rc) return rc;
-        rc = c->alloc(d_val, 16ull * n, "gather values"); if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(d_idx.p, idx.data(), 8ull * n, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_gather_u64, dim3((2 * n + 255) / 256), dim3(256), 0, c->stream, (const uint64_t*)P.ipre.p,
-                           (const uint32_t*)d_idx.p, 2 * n, (uint64_t*)d_val.p);
-        HIP_TRY(hipGetLastError());
-        std::vector<uint64_t> val(2 * n);
-        HIP_TRY(hipMemcpyAsync(val.data(), d_val.p, 16ull * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->release(d_idx); c->release(d_val);
-        std::vector<ItemRange> sub_items, huge; std::vector<uint32_t> sub_words;
-        constexpr uint64_t PER_SUB = (1ull << CountCfg<K>::LOG2S) / 2;
-        constexpr uint32_t MAX_P = 8;                                    // selector bits (wave_count_chunk)
-        static const uint32_t max_lds_p = getenv("DFK_MAX_SUBPASS_LOG2") ? (uint32_t)atoi(getenv("DFK_MAX_SUBPASS_LOG2")) : 8;
-        // p is first guessed from the distinct k-mers per instance seen so far (a repeat-rich bucket has far fewer
-        // distinct k-mers than instances); a sub-pass that overflows anyway is cut in two by one more selector bit
-        // and counted again -- its siblings are done and stay -- until p = MAX_P, where 1024 *instances* per sub-pass
-        // are guaranteed.
-        const double dpi = c->distinct_per_inst > 0.0 ? std::min(1.0, 2.0 * c->distinct_per_inst) : 0.5;   // (first pass: a guess)
-        // Buckets that would need four sub-passes or more (each sub-pass reads and extracts ALL of the bucket's
-        // instances again: work quadratic in the bucket's size, 6 s of a 9.5 s step at human scale with a 10 % repeat
-        // family) are partitioned a second time instead, by k-mer hash (count_split): linear work.
-        static const uint32_t split_from_p = getenv("DFK_SPLIT_FROM_LOG2") ? (uint32_t)atoi(getenv("DFK_SPLIT_FROM_LOG2")) : 2;
-        std::vector<ItemRange> sp_b; std::vector<uint64_t> sp_i; std::vector<uint32_t> sp_p; std::vector<uint32_t> sp_at;
-        for (uint32_t i = 0; i < n; ++i) {
-            const uint64_t inst = val[2 * i + 1] - val[2 * i];
-            const uint64_t guess = (uint64_t)((double)inst * dpi) + 1;
-            const uint32_t p = ceil_log2((guess + 699) / 700);
-            // (k_hot_pass keeps a record's place inside its hot bucket in 32 bits: a bucket of 2^32 instances or more -- whatever
-            // its distinct k-mers -- takes the HBM tables)
-            if (p >= split_from_p && p <= 22 && inst < (1ull << 32)) { sp_b.push_back(singles[i]); sp_i.push_back(inst); sp_p.push_back(p); sp_at.push_back(i); }
-        }
-        std::vector<uint8_t> taken(n, 0);
-        // The expanded records of the split buckets (32 B per instance: 30 GB for a pass of a human-scale set with a 10 %
-        // repeat family) must fit one free block of the arena, which the pass plan does not reserve: the buckets are
-        // split in as many groups as that takes.  (All at once or not at all, three passes in twenty found no block
-        // and fell back to 250 000 sub-passes and HBM tables: 0.45 s each.)
-        for (size_t i0 = 0; i0 < sp_b.size();) {
-            const uint64_t can = c->largest_allocatable(), keep = 512ull << 20;
-            const uint64_t cap_inst = can > keep ? (uint64_t)(0.95 * (double)(can - keep)) / 34 : 0;
-            size_t i1 = i0; uint64_t sum = 0;
-            while (i1 < sp_b.size() && sum + sp_i[i1] <= cap_inst) sum += sp_i[i1++];
-            if (i1 == i0) { TRACE("fallback: no room to split a hot bucket of %llu instances (%.2f GB free in one piece): sub-passes instead", (unsigned long long)sp_i[i0], can / 1e9); break; }
-            const std::vector<ItemRange> gb(sp_b.begin() + i0, sp_b.begin() + i1);
-            const std::vector<uint64_t> gi(sp_i.begin() + i0, sp_i.begin() + i1);
-            const std::vector<uint32_t> gp(sp_p.begin() + i0, sp_p.begin() + i1);
-            const int r2 = count_split<K, NBC>(c, P, gb, gi, gp, R);
-            if (r2 == 0) { for (size_t i = i0; i < i1; ++i) taken[sp_at[i]] = 1; i0 = i1; }
-            else if (r2 != E_SPLIT_NO_ROOM) return r2;
-            else { TRACE("fallback: no room to split %zu hot buckets (%s): sub-passes instead", i1 - i0, g_err.c_str()); break; }
-        }
-        for (uint32_t i = 0; i < n; ++i) {
-            if (taken[i]) continue;
-            const uint64_t inst = val[2 * i + 1] - val[2 * i];
-            // (beyond MAX_P selector bits x 1024 instances the refinement below could not be guaranteed to end)
-            if (ceil_log2((inst + PER_SUB - 1) / PER_SUB) > MAX_P) { huge.push_back(singles[i]); continue; }
-            const uint64_t guess = (uint64_t)((double)inst * dpi) + 1;
-            const uint32_t p = std::max<uint32_t>(1, ceil_log2((guess + PER_SUB - 1) / PER_SUB));
-            // Every sub-pass reads and extracts ALL of the bucket's instances again: 2^p-fold work, quadratic in the
-            // bucket's size -- at human scale with a 10 % repeat family the sub-passes take 6 s of a 9.5 s step.  The
-            // HBM tables are no way out as they stand: k_big_insert runs at 1.8 G instances/s there (four dependent
-            // agent-scope atomics per instance, acquire/release fences per probe: 245 ms per pass), 8.7 s per step when
-            // every bucket beyond four sub-passes goes to them (DFK_MAX_SUBPASS_LOG2=2).  What such buckets want is a
-            // second-level partition by k-mer hash into buckets that fit LDS tables.
-            if (p > max_lds_p) { huge.push_back(singles[i]); continue; }
-            for (uint32_t k = 0; k < (1u << p); ++k) { sub_items.push_back(singles[i]); sub_words.push_back((p << 8) | k); }
-        }
-        TRACE("fallback: %zu sub-passes over %zu buckets in LDS tables, %zu buckets in HBM tables", sub_items.size(), singles.size() - huge.size(), huge.size());
-        while (!sub_items.empty()) {
-            DevBuf d_it, d_sub;
-            rc = c->alloc(d_it, sub_items.size() * sizeof(ItemRange), "sub-pass items"); if (rc) return rc;
-            rc = c->alloc(d_sub, sub_words.size() * 4, "sub-pass words"); if (rc) return rc;
-            HIP_TRY(hipMemcpyAsync(d_it.p, sub_items.data(), sub_items.size() * sizeof(ItemRange), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(d_sub.p, sub_words.data(), sub_words.size() * 4, hipMemcpyHostToDevice, c->stream));
-            std::vector<ItemRange> again;
-            float ignored = 0;
-            rc = launch_count<K, NBC>(c, P, (const ItemRange*)d_it.p, sub_items.size(), R, &again, &ignored, (const uint32_t*)d_sub.p);
-            c->release(d_it); c->release(d_sub);
-            if (rc) return rc;
-            sub_items.clear(); sub_words.clear();
-            for (const ItemRange& r : again) {                           // {bucket, 0x80000000 | sub-pass word}
-                const uint32_t w = r.b1 & 0x7FFFFFFFu, p = w >> 8, k = w & 0xFFu;
-                if (!(r.b1 & 0x80000000u) || p >= MAX_P)
-                    return fail(DFK_E_HIP, "a sub-pass (%u of 2^%u) of bucket %u overflowed its table (it holds at most %llu instances)", k, p, r.b0, (unsigned long long)PER_SUB);
-                sub_items.push_back(ItemRange{r.b0, r.b0 + 1}); sub_words.push_back(((p + 1) << 8) | k);
-                sub_items.push_back(ItemRange{r.b0, r.b0 + 1}); sub_words.push_back(((p + 1) << 8) | (k + (1u << p)));
-            }
-            if (!sub_items.empty()) TRACE("fallback: %zu sub-passes cut in two", again.size());
-        }
-        if (!huge.empty()) { rc = launch_count_big<K, NBC>(c, P, huge, R); if (rc) return rc; }
-    }
-    c->st.ms_fallback += t.stop();
-
     CountGlobals hg{};
     std::vector<WgOut> wg(R.grid);
     HIP_TRY(hipMemcpy(&hg, R.d_g.p, sizeof hg, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(wg.data(), R.d_wg.p, sizeof(WgOut) * R.grid, hipMemcpyDeviceToHost));
     c->release(R.d_wg);
-    const uint64_t CH = out_chunk<K>(), claimed = hg.part_cursor;
-    // the holes: the unused end of every workgroup's last chunk
-    std::vector<std::pair<uint64_t, uint64_t>> holes;
-    uint64_t n_holes = 0;
-    for (const WgOut& w : wg) if (w.chunk != ~0ull && w.used < CH) { holes.push_back({w.chunk + w.used, w.chunk + CH}); n_holes += CH - w.used; }
-    const uint64_t n_lds = claimed - n_holes;                          // solid k-mers the LDS path emitted
+    const uint64_t claimed = hg.part_cursor;
+    const HoleMoves mv = plan_hole_moves(wg, out_chunk<K>(), claimed);
+    const std::vector<uint64_t>&src = mv.src, &dst = mv.dst; const uint64_t n_lds = mv.n_lds;   // n_lds: solid k-mers the LDS path emitted
     if (hg.solid_overflow || claimed > R.cp.seg_cap || hg.big_cursor > R.big_cap || n_lds + hg.big_cursor > R.cp.seg_cap) {
         // the caller undoes the pass and redoes it with more room
         c->release(R.big); c->release(R.d_part);
         fail(DFK_E_NOMEM, "the room reserved for a pass's solid k-mers (%llu entries) is full", (unsigned long long)R.cp.seg_cap);
         return E_SEGMENT_FULL;
-    }
-    // entries beyond n_lds move into the holes below n_lds: afterwards [0, n_lds) is dense
-    std::sort(holes.begin(), holes.end());
-    std::vector<uint64_t> dst, src;
-    for (const auto& h : holes) for (uint64_t i = h.first; i < std::min(h.second, n_lds); ++i) dst.push_back(i);
-    {
-        size_t hi = 0;
-        for (uint64_t i = n_lds; i < claimed && src.size() < dst.size(); ++i) {
-            while (hi < holes.size() && holes[hi].second <= i) ++hi;
-            if (hi < holes.size() && holes[hi].first <= i) { i = holes[hi].second - 1; continue; }   // skip a hole
-            src.push_back(i);
-        }
     }
     if (src.size() != dst.size())
         return fail(DFK_E_HIP, "output compaction: %zu holes, %zu entries to move", dst.size(), src.size());
@@ -1283,7 +1102,7 @@ int count_run(dfk_ctx* c, const Partition& P, CountRun& R)
     part.n = n_lds + hg.big_cursor;
     part.buf = R.d_part; R.d_part = DevBuf{};
     if (!src.empty()) {
-        DevBuf d_mv; rc = c->alloc(d_mv, 16ull * src.size(), "hole moves"); if (rc) return rc;
+        DevBuf d_mv; int rc = c->alloc(d_mv, 16ull * src.size(), "hole moves"); if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(d_mv.p, src.data(), 8ull * src.size(), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync((uint64_t*)d_mv.p + src.size(), dst.data(), 8ull * src.size(), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_fill_holes, dim3((unsigned)((src.size() + 255) / 256)), dim3(256), 0, c->stream, (uint4*)part.buf.p,
@@ -1300,7 +1119,7 @@ int count_run(dfk_ctx* c, const Partition& P, CountRun& R)
     // 4 bytes for one entry in eight); it is filled on the second stream while the next pass is counted
     const uint64_t nb_part = hg.n_boundary - R.boundary_seen;
     R.boundary_seen = hg.n_boundary;
-    c->st.n_overflow_items += hg.n_split - R.splits_seen;             // (+ the single buckets that went to HBM tables, above)
+    c->st.n_overflow_items += hg.n_split - R.splits_seen;             // (+ the items that overflowed a launch, counted by count_run)
     R.splits_seen = hg.n_split;
     uint64_t keep = part.n * 32;
     part.listed = c->want_blist && nb_part == 0;
@@ -1317,21 +1136,80 @@ int count_run(dfk_ctx* c, const Partition& P, CountRun& R)
     return 0;
 }
 
+// Count one pass: k_count over its items, the items that overflowed their LDS table by the routes of dfk_fallback.h
+// (halved; single fine buckets split by k-mer hash, counted in sub-passes or in HBM tables), then the pass's solid
+// k-mers as a dense part.
+template <int K, int NBC>
+int count_run(dfk_ctx* c, const Partition& P, CountRun& R)
+{
+    Timer t(c->stream);
+    std::vector<ItemRange> overflowed, singles;
+    c->st.n_items += P.n_items;
+    const float ms_before = c->st.ms_count;
+    int rc = launch_count<K, NBC>(c, P, (const ItemRange*)P.items.p, P.n_items, R, &overflowed, &c->st.ms_count); if (rc) return rc;
+    if (g_trace) {
+        unsigned int gate[2] = {0, 0};
+        (void)hipMemcpy(gate, c->d_resident, 8, hipMemcpyDeviceToHost);
+        TRACE("k_count: %llu instances in %.1f ms (%.1f G instances/s), reservation %.2f GB, %u of %u workgroups idle, %u gate timeouts so far",
+              (unsigned long long)P.n_inst, c->st.ms_count - ms_before, 1e-6 * (double)P.n_inst / (double)(c->st.ms_count - ms_before), R.d_part.bytes / 1e9,
+              c->last_wg_idle, R.grid, gate[1]);
+    }
+    t.start();
+    c->st.n_overflow_items += overflowed.size();
+    rc = count_halved<K, NBC>(c, P, R, false, overflowed, &singles); if (rc) return rc;
+    TRACE("fallback: %zu single-bucket items", singles.size());
+    if (!singles.empty()) {
+        const FallbackSwitches sw{env_u32("DFK_SPLIT_FROM_LOG2", 2), env_u32("DFK_MAX_SUBPASS_LOG2", 8)};
+        const double dpi = route_distinct_per_inst(c->distinct_per_inst);
+        std::vector<uint64_t> inst; std::vector<uint8_t> taken(singles.size(), 0);   // instances of every single bucket; 1: counted by a split
+        rc = gather_diffs(c, singles, {{&P.ipre, &inst}}); if (rc) return rc;
+        // split groups: as many candidates at a time as the arena's largest free block holds; where a group finds no room,
+        // the buckets left keep their other routes
+        const SplitCandidates sp = split_candidates(inst, dpi, sw);
+        for (size_t i0 = 0; i0 < sp.at.size();) {
+            const uint64_t can = c->largest_allocatable();
+            const size_t i1 = split_group_end(inst, sp.at, i0, split_group_cap(can));
+            if (i1 == i0) { TRACE("fallback: no room to split a hot bucket of %llu instances (%.2f GB free in one piece): sub-passes instead", (unsigned long long)inst[sp.at[i0]], can / 1e9); break; }
+            rc = count_split<K, NBC>(c, P, singles, inst, sp, i0, i1, R);
+            if (rc == E_SPLIT_NO_ROOM) { TRACE("fallback: no room to split %zu hot buckets (%s): sub-passes instead", i1 - i0, g_err.c_str()); break; }
+            if (rc) return rc;
+            for (; i0 < i1; ++i0) taken[sp.at[i0]] = 1;
+        }
+        // sub-passes, those that overflow again cut in two until none does
+        SubpassPlan sub = plan_subpasses(singles, inst, taken, dpi, CountCfg<K>::LOG2S, sw);
+        TRACE("fallback: %zu sub-passes over %zu buckets in LDS tables, %zu buckets in HBM tables", sub.items.size(), singles.size() - sub.huge.size(), sub.huge.size());
+        while (!sub.items.empty()) {
+            DevBuf d_it, d_sub;
+            rc = c->alloc(d_it, sub.items.size() * sizeof(ItemRange), "sub-pass items"); if (!rc) rc = c->alloc(d_sub, sub.words.size() * 4, "sub-pass words"); if (rc) return rc;
+            HIP_TRY(hipMemcpyAsync(d_it.p, sub.items.data(), sub.items.size() * sizeof(ItemRange), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(d_sub.p, sub.words.data(), sub.words.size() * 4, hipMemcpyHostToDevice, c->stream));
+            std::vector<ItemRange> again; ItemRange bad{}; float ignored = 0;
+            rc = launch_count<K, NBC>(c, P, (const ItemRange*)d_it.p, sub.items.size(), R, &again, &ignored, (const uint32_t*)d_sub.p);
+            c->release(d_it); c->release(d_sub);
+            if (rc) return rc;
+            if (!refine_subpasses(again, &sub, &bad))
+                return fail(DFK_E_HIP, "a sub-pass (%u of 2^%u) of bucket %u overflowed its table (it holds at most %llu instances)", bad.b1 & 0xFFu, (bad.b1 & 0x7FFFFFFFu) >> 8, bad.b0, 1ull << (CountCfg<K>::LOG2S - 1));
+            if (!sub.items.empty()) TRACE("fallback: %zu sub-passes cut in two", again.size());
+        }
+        if (!sub.huge.empty()) { rc = launch_count_big<K, NBC>(c, P, sub.huge, R); if (rc) return rc; }
+    }
+    c->st.ms_fallback += t.stop();
+    return finish_part<K>(c, P, R);
+}
+
+
+template <int K>
+int count_run_nbc(dfk_ctx* c, const Partition& P, CountRun& R, int nbc)   // nbc: barcode_words
+{
+    static int (*const run[8])(dfk_ctx*, const Partition&, CountRun&) = {count_run<K, 0>, count_run<K, 1>, count_run<K, 2>, count_run<K, 3>, count_run<K, 4>, count_run<K, 5>, count_run<K, 6>, count_run<K, 7>};
+    return run[std::min(std::max(nbc, 0), 7)](c, P, R);
+}
 
 template <int K>
 int stage_count(dfk_ctx* c, const Partition& P, CountRun& R, bool have_bc)
 {
-    int rc = count_prepare<K>(c, P, R, barcode_words(c, have_bc)); if (rc) return rc;
-    switch (barcode_words(c, have_bc)) {
-    case 0: return count_run<K, 0>(c, P, R);
-    case 1: return count_run<K, 1>(c, P, R);
-    case 2: return count_run<K, 2>(c, P, R);
-    case 3: return count_run<K, 3>(c, P, R);
-    case 4: return count_run<K, 4>(c, P, R);
-    case 5: return count_run<K, 5>(c, P, R);
-    case 6: return count_run<K, 6>(c, P, R);
-    default: return count_run<K, 7>(c, P, R);
-    }
+    const int rc = count_prepare<K>(c, P, R, barcode_words(c, have_bc));
+    return rc ? rc : count_run_nbc<K>(c, P, R, barcode_words(c, have_bc));
 }
 
 // ------------------------------------------------------------------ stage: adjacency (a6)
@@ -1558,18 +1436,7 @@ int run_typed(dfk_ctx* c, const Inputs& in, Prescan* pre = nullptr)
                 if (r2 && r2 != DFK_E_NOMEM) return r2;                // NOMEM: this range is scattered after the count instead
             }
         }
-        if (!rc) {
-            switch (barcode_words(c, in.bc != nullptr)) {               // barcodes a table slot remembers: max(1, MIN_BC - 1)
-            case 0: rc = count_run<K, 0>(c, cur.sj.P, R); break;
-            case 1: rc = count_run<K, 1>(c, cur.sj.P, R); break;
-            case 2: rc = count_run<K, 2>(c, cur.sj.P, R); break;
-            case 3: rc = count_run<K, 3>(c, cur.sj.P, R); break;
-            case 4: rc = count_run<K, 4>(c, cur.sj.P, R); break;
-            case 5: rc = count_run<K, 5>(c, cur.sj.P, R); break;
-            case 6: rc = count_run<K, 6>(c, cur.sj.P, R); break;
-            default: rc = count_run<K, 7>(c, cur.sj.P, R); break;
-            }
-        }
+        if (!rc) rc = count_run_nbc<K>(c, cur.sj.P, R, barcode_words(c, in.bc != nullptr));
         if (c->after_count_launch) {                                     // (no k_count was launched: an error on the way there)
             std::function<int()> f; f.swap(c->after_count_launch);
             if (!rc) { const int r3 = f(); if (r3) return r3; } else nxt.valid = false;

@@ -4,6 +4,7 @@
 #pragma once
 #include <type_traits>
 #include "dfk_device.h"
+#include "dfk_fallback.h"   // ItemRange, WgOut, HotItem, BigItem, COUNT_CHUNK: what the kernels share with the host's fallback planner
 
 namespace dfk {
 
@@ -973,8 +974,6 @@ k_scatter_runs(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const 
 // After the item, solid slots are compacted to the output and the spectrum is updated.
 
 
-struct ItemRange { uint32_t b0, b1; };     // a work item: fine buckets [b0,b1) of the current pass
-
 struct CountParams {
     uint32_t min_freq, min_bc;
     uint32_t n_items;
@@ -997,16 +996,9 @@ struct CountGlobals {                // device-resident counters
     unsigned int pad_idle;
 };
 
-// Where a persistent workgroup is in the chunk of the output buffer it is filling (kept across the launches of
-// one pass).  Workgroups take chunks of OUT_CHUNK entries from CountGlobals::part_cursor and fill them item by
-// item, an item's entries running over into a fresh chunk when needed; only the last chunk of every workgroup
-// is left partly empty, and the host moves entries from the tail into those holes.
-struct WgOut { unsigned long long chunk; unsigned int used; unsigned int pad; };
-
 constexpr int COUNT_HIST_BINS = 256;             // spectrum bins kept in LDS; higher counts go straight to the global bins
 constexpr uint32_t COUNT_MAX_PROBE = 96;
 constexpr uint32_t HIST_GLOBAL_BINS = 1u << 24;   // KDef count saturates at 2^24-1 (ReadPather.h:128-129)
-constexpr int COUNT_CHUNK = 32;                   // records a wave stages at a time
 constexpr uint32_t FLAG_SOLID = 0x80000000u;      // barcode word reused after counting: solid flag | unresolved context bits
 
 template <int K> struct WaveStage {               // per-wave private LDS
@@ -1305,7 +1297,6 @@ __device__ __forceinline__ uint32_t big_find(const uint64_t* __restrict__ pre, u
 // instance of a k-mer lands in the same sub-bucket, a sub-bucket holds ~700 distinct k-mers, and the sub-buckets are
 // then counted by the ordinary k_count as the buckets of a small pass of their own.  Work linear in the bucket's
 // instances -- counting it as 2^p sub-passes over the same records extracts every instance 2^p times.
-struct HotItem { uint32_t b0, b1; uint32_t sub_base; uint32_t log2p; };
 
 __device__ __forceinline__ uint32_t sub_bucket_hash(const Probe& A)
 {
@@ -1860,7 +1851,6 @@ constexpr size_t count_lds_bytes()
 //   k_big_flags    per slot: solid or not
 //   k_big_resolve  per solid slot and context bit: neighbour in the same table?  (as table_finish pass 2)
 //   k_big_emit     solid slots to the fallback's output buffer through a global cursor, spectrum, counters
-struct BigItem { uint32_t b0, b1; uint64_t tab_off; uint32_t log2s; uint32_t pad; };
 template <int K, int NWAVES, int NBC>
 __global__ void __launch_bounds__(NWAVES * 64)
 k_big_insert(const uint4* __restrict__ records, const BigItem* __restrict__ items, const uint64_t* __restrict__ rec_base,

@@ -80,6 +80,31 @@ def test_golden_hot_minimizer_through_abi(golden_dir, kw):
     d.close()
 
 
+@pytest.mark.parametrize("switches", [dict(), dict(DFK_SPLIT_FROM_LOG2="20"), dict(DFK_SPLIT_FROM_LOG2="20", DFK_MAX_SUBPASS_LOG2="0")],
+                         ids=["default", "no_split", "no_split_no_subpasses"])
+def test_golden_hot_minimizer_by_every_fallback_route(golden_dir, monkeypatch, switches):
+    """The hot-minimizer fixture of test_golden_hot_minimizer_through_abi under the switches that choose the route of
+    an overflowing fine bucket (read at every count; dfk_fallback.h states the routes).  The input is counted in one
+    pass, so the routes are planned with the first pass's guess of 0.5 distinct k-mers per instance; its hot bucket (the
+    rank-0 minimizer, in 1201 of the 1500 reads) holds some 39 600 instances.  By the header's rules that makes -- default: split by k-mer hash into 2^5
+    sub-buckets (count_split).  DFK_SPLIT_FROM_LOG2=20: no split (that asks for 2^20 sub-buckets of 700 k-mers), 2^5
+    sub-passes in LDS tables.  With DFK_MAX_SUBPASS_LOG2=0 as well: an HBM table."""
+    from superplus_amd.dfk import Dfk
+    from tests.test_oracle_golden import load_hot
+    for name, value in switches.items():
+        monkeypatch.setenv(name, value)
+    rs = load_hot(golden_dir)
+    exp = np.load(os.path.join(golden_dir, "expect_hot_k48_minfreq2.npz"))
+    d = Dfk(K=48, min_freq=2, keep_pre_adjacency=True)
+    d.count(rs["packed"], rs["base_off"], rs["read_len"], rs["pq_bytes"], rs["pq_off"], rs["bc"])
+    assert np.array_equal(d.good_lens(), exp["good_len"])
+    util.assert_same_solid(d.solid(pre_adjacency=True), exp["solid_pre"], "hot: kvec view")
+    util.assert_same_solid(d.solid(), exp["solid_post"], "hot: Dict view")
+    assert np.array_equal(d.spectrum(), exp["spectrum"])
+    assert d.stats()["n_overflow_items"] > 0
+    d.close()
+
+
 @pytest.mark.parametrize("min_freq,min_bc,use_bc,ign", [(1, 2, True, 0), (2, 0, True, 0), (3, 1, True, 0), (3, 2, False, 0),
                                                        (3, 2, True, 2000), (5, 2, True, 10**9),
                                                        (3, 3, True, 0), (3, 4, True, 0), (2, 3, True, 2000)])
