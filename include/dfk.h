@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DFK_ABI_VERSION 1
+#define DFK_ABI_VERSION 2
 #define DFK_MAX_MIN_BC 8u
 
 enum {
@@ -299,6 +299,51 @@ int dfk_paths_index_dups_write(dfk_ctx* ctx, const char* dir, const char* dup_pa
 int dfk_bads_sums(dfk_ctx* ctx, uint16_t* out, uint64_t cap);
 int dfk_bads_write(dfk_ctx* ctx, const char* path, uint64_t* n_marked_pairs, uint64_t* digest /* [2] or NULL */);
 int dfk_bads_write_part(dfk_ctx* ctx, const char* path, uint64_t first_pair, uint64_t total_pairs, uint64_t* n_marked, uint64_t* digest /* [2] or NULL */);
+
+/* ---- the second step of the patching stage: FindEdgePairs (10X/Closomatic.cc:17-358, called by StagePatch,
+ * 10X/runstages/RunStages.cc:204-205; written as a.<K>/a.hops, 10X/DF.cc:603) ----
+ * Chooses the pairs of graph edges (e1, e2) the gap closer will try to join, by three methods (stated in csrc/dfk_hops.h):
+ * an e1 near a sink whose reads' mates end on one e2 under two barcodes (methods 1 and 2), and an edge that the reads on it
+ * and on its involution cannot extend by 100 k-mers, with the edges its not-bad reads' mates see under two barcodes (method 3).
+ * It reads what dfk_paths_build* left on the device -- the paths, the graph's tables, MarkBads' sums -- and one barcode id per
+ * read (bid = N + bc[id]: only equality matters, so bc itself, or the .bci index as dfk_count_bci reads it).  The reference walks
+ * a.paths.inv from disk three times with all paths in host memory.
+ *   dfk_hops_build      builds the pairs: a combined index of the reads on an edge and on its involution, a range of edges at a
+ *                       time (the ranges of the paths index); methods 1 and 2 through an open-address table; method 3 a wave per
+ *                       edge with its sets in LDS.  An edge whose sets outgrow the capacities (DFK_HOPS_MAX_SEQS sequences of
+ *                       DFK_HOPS_MAX_LEN edges, read from the environment) is never truncated: the host decides it exactly and
+ *                       the call counts it.  one_good: the reference's ONE_GOOD (method 1 without the source test).  Holds no
+ *                       device memory when it returns; the sorted pairs stay in host memory.  Negative barcodes and an odd
+ *                       number of reads are DFK_E_ARG.
+ *   dfk_hops_build_bci  the same from the barcode index
+ *   dfk_hops_stats      out[DFK_HOPS_WORDS]: the counters below
+ *   dfk_hops_fetch      the pairs, two int32 each, sorted; pairs NULL and cap 0 = the count alone
+ *   dfk_hops_write      a.hops ("BINWRITE" | u64 n | n x (i32, i32)); path NULL = everything but the file; digest (or NULL) = sum
+ *                       and xor over the pairs of a 64-bit mix of (first << 32 | second)
+ * Valid from dfk_paths_build* on a context created with DFK_F_MARK_BADS until the paths are dropped, before or after
+ * dfk_paths_index_write / dfk_dups_write / dfk_bads_write; otherwise DFK_E_STATE.  Not for the ranks of a sharded run: method 3
+ * needs the paths of every read on an edge and on its involution in one place. */
+#define DFK_HOPS_WORDS 16
+#define DFK_HOPS_M1 0            /* pairs of method 1, 2, 3 (each a set) ... */
+#define DFK_HOPS_M2 1
+#define DFK_HOPS_M3 2
+#define DFK_HOPS_PAIRS 3         /* ... and of their union: what a.hops holds */
+#define DFK_HOPS_SEARCHED 4      /* edges that reached method 3's search */
+#define DFK_HOPS_EXTENDED 5      /* ... of which extended */
+#define DFK_HOPS_HOST_EDGES 6    /* ... of which decided on the host (their sets did not fit) */
+#define DFK_HOPS_MOST_ROUNDS 7
+#define DFK_HOPS_US 8            /* microseconds: the call, */
+#define DFK_HOPS_US_INDEX 9      /* the combined index's kernels, */
+#define DFK_HOPS_US_M12 10       /* the kernels of methods 1 and 2, */
+#define DFK_HOPS_US_M3 11        /* the kernel of method 3, */
+#define DFK_HOPS_US_HOST 12      /* the host's exact route (wall) */
+#define DFK_HOPS_LARGEST_X 13
+#define DFK_HOPS_RANGES 14
+int dfk_hops_build(dfk_ctx* ctx, const int32_t* bc /* [n_reads], host */, int one_good);
+int dfk_hops_build_bci(dfk_ctx* ctx, const int64_t* bci, uint64_t n_bci, int one_good);
+int dfk_hops_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_HOPS_WORDS] */);
+int dfk_hops_fetch(dfk_ctx* ctx, int32_t* pairs /* 2 per pair */, uint64_t cap, uint64_t* n_pairs);
+int dfk_hops_write(dfk_ctx* ctx, const char* path /* NULL = all but the file */, uint64_t* n_pairs, uint64_t* digest /* [2] or NULL */);
 
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).

@@ -551,7 +551,8 @@ int main(int argc, char** argv)
     std::map<std::string, std::string> a = {
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
-        {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"}};
+        {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -569,6 +570,11 @@ int main(int argc, char** argv)
         g_threads = nt > 0 ? (unsigned)nt : std::max(1u, std::thread::hardware_concurrency());
         g_threads = std::min(g_threads, 64u);
     }
+
+    // HOPS=True (FindEdgePairs, a.<K>/a.hops) is for one GPU: method 3 needs the paths of every read on an edge and on its
+    // involution in one place.  Refused here, before a directory is made or a GPU is touched.
+    if (truthy(a["HOPS"]) && (atoi(a["NUM_GPUS"].c_str()) > 1 || getenv("DF_FORCE_SHARDED") || (getenv("DF_TRANSPORT") && std::string(getenv("DF_TRANSPORT")) == "loopback")))
+        give_up("HOPS=True runs on one GPU only (no NUM_GPUS > 1, DF_FORCE_SHARDED or DF_TRANSPORT=loopback): FindEdgePairs needs every read's path in one place");
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -783,7 +789,8 @@ int main(int argc, char** argv)
         const bool want_kvec = a["KVEC"] == "Auto" ? (!truthy(a["GRAPH"]) || truthy(a["KVEC_SORTED"])) : truthy(a["KVEC"]);
         if (want_paths) cfg.flags |= DFK_F_KEEP_INPUTS;                          // the reads stay on the device for pathReads
         const bool want_bads = want_paths && truthy(a["BADS"]);
-        if (want_bads) cfg.flags |= DFK_F_MARK_BADS;                             // ... and MarkBads' sums are gathered while they are pathed
+        const bool want_hops = want_paths && truthy(a["HOPS"]);                  // FindEdgePairs takes MarkBads' marks: HOPS gathers them too (a.bad itself is BADS' business)
+        if (want_bads || want_hops) cfg.flags |= DFK_F_MARK_BADS;                             // ... and MarkBads' sums are gathered while they are pathed
         // a.<K>/a.paths and a.paths.inv are the stage's largest outputs (20-odd and 8 bytes a read: 37 and 14 GB at configs[1]) and
         // their sizes are known only once the reads are pathed.  Pages for them are made NOW (PATHS_RESERVE bytes a read for
         // a.paths -- 16 fixed and one path entry -- and 8 for every entry that leaves for a.paths.inv; 0 = don't), by threads nobody
@@ -992,6 +999,16 @@ int main(int argc, char** argv)
                     uint64_t n_bad = 0, bd[2] = {0, 0};
                     if (dfk_bads_write(ctx, (dir + "/a.bad").c_str(), &n_bad, bd)) throw std::runtime_error(dfk_last_error());
                     print_bads(n_bad, n_reads / 2, bd);
+                }
+                if (want_hops) {                                               // FindEdgePairs (StagePatch, RunStages.cc:204-205): a.<K>/a.hops (10X/DF.cc:603), after a.bad
+                    printf("%s: start looking for edge pairs\n", date().c_str());
+                    uint64_t n_hops = 0, hd[2] = {0, 0}, hs[DFK_HOPS_WORDS] = {};
+                    if (dfk_hops_build_bci(ctx, bci.data(), bci.size(), truthy(a["ONE_GOOD"]) ? 1 : 0) || dfk_hops_write(ctx, (dir + "/a.hops").c_str(), &n_hops, hd) ||
+                        dfk_hops_stats(ctx, hs)) throw std::runtime_error(dfk_last_error());
+                    printf("pairs.size( ) = %llu\n", (unsigned long long)n_hops);            // Closomatic.cc:347
+                    printf("DF_HOPS {\"a.hops\": \"%016llx%016llx\", \"pairs\": %llu, \"m1\": %llu, \"m2\": %llu, \"m3\": %llu, \"host_edges\": %llu}\n", (unsigned long long)hd[0],
+                           (unsigned long long)hd[1], (unsigned long long)n_hops, (unsigned long long)hs[DFK_HOPS_M1], (unsigned long long)hs[DFK_HOPS_M2],
+                           (unsigned long long)hs[DFK_HOPS_M3], (unsigned long long)hs[DFK_HOPS_HOST_EDGES]);
                 }
             }
             t_g_write = tw_graph;

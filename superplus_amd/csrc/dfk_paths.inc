@@ -34,6 +34,8 @@ struct PathState {
     uint64_t n_reads = 0, n_placed = 0, n_edges = 0, var_total = 0;
     DevBuf digest;                                    // u32[n_reads]: first five bases | quality sum << 10 (k_read_digest), for MarkDups
     DevBuf bad_sums;                                  // u16[n_reads]: MarkBads' per-read sums (k_bad_sums), under DFK_F_MARK_BADS only
+    std::vector<int32_t> hops;                        // FindEdgePairs' sorted pairs, two words each (dfk_hops_build, dfk_hops.inc): host memory
+    uint64_t hops_stats[DFK_HOPS_WORDS] = {}; bool hops_valid = false;
     uint64_t ck[DFK_CHECK_WORDS] = {};                // dfk_paths_digest: what the steps so far have left (ck[DFK_CK_VALID]: which)
     int64_t read_id0 = 0;                             // a rank of a sharded run: the whole set's number of its first read (dfk_paths_shard.inc)
     void* shard = nullptr; void (*shard_free)(void*) = nullptr;
@@ -48,6 +50,7 @@ void paths_drop_results(dfk_ctx* c, PathState* P)
     for (PathBatch& b : P->batches) { c->release(b.var); c->release(b.elem_off); }
     c->release(P->digest); c->release(P->bad_sums);
     P->batches.clear(); P->built = false; P->n_reads = P->n_placed = P->n_edges = P->var_total = 0;
+    P->hops.clear(); P->hops_valid = false;
     for (uint64_t& w : P->ck) w = 0;
 }
 

@@ -13,7 +13,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DFK_LIB") or os.path.join(_HERE, "libdfk.so")      # DFK_LIB: a developer's timing variant (tools/)
-ABI_VERSION = 1
+ABI_VERSION = 2
 F_KEEP_PRE_ADJ = 1
 F_KEEP_INPUTS = 2
 F_MARK_BADS = 4
@@ -31,6 +31,7 @@ EXPORTS = [
     "dfk_paths_digest", "dfk_paths_verify", "dfk_paths_verify_device", "dfk_pbf_run", "dfk_pbf_result", "dfk_pbf_free",
     "dfk_paths_var_bytes", "dfk_paths_write_part", "dfk_shard_pidx_pairs", "dfk_shard_pidx_write", "dfk_shard_dup_keys", "dfk_shard_dup_answer", "dfk_shard_dup_write",
     "dfk_bads_sums", "dfk_bads_write", "dfk_bads_write_part",
+    "dfk_hops_build", "dfk_hops_build_bci", "dfk_hops_stats", "dfk_hops_fetch", "dfk_hops_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -38,6 +39,9 @@ CHECK_WORDS = 20
 CK = ["PATHS_SUM", "PATHS_XOR", "N_READS", "N_PLACED", "N_PATH_EDGES", "INV_SUM", "INV_XOR", "INV_STARTS", "INV_ENTRIES",
       "COUNTSB_DIGEST", "COUNTSB_SUM", "SELF_INVERSE", "DUP_DIGEST", "DUP_MARKED", "EDGE_KMERS", "N_SOLID", "INV_VIOLATIONS",
       "N_EDGES", "VALID"]
+# dfk_hops_stats' words (include/dfk.h, DFK_HOPS_*)
+HOPS_WORDS = 16
+HOPS = ["m1", "m2", "m3", "pairs", "searched", "extended", "host_edges", "most_rounds", "us", "us_index", "us_m12", "us_m3", "us_host", "largest_x", "ranges"]
 VERIFY = ["placed", "broken", "hits", "consistent", "no_anchor", "all_consistent", "dict_bad", "outside"]
 
 
@@ -289,6 +293,38 @@ class Dfk:
         """a.bad (MarkBads); returns (pairs marked, (sum, xor) digest of the per-read sums).  None = no file."""
         n = C.c_uint64(); dg = (C.c_uint64 * 2)()
         _check(lib().dfk_bads_write(self._ctx, None if path is None else path.encode(), C.byref(n), dg))
+        return n.value, (int(dg[0]), int(dg[1]))
+
+    def hops_build(self, bc, one_good=False):
+        """dfk_hops_build: FindEdgePairs from the paths, MarkBads' sums (mark_bads=True) and one barcode per read; returns hops_stats()."""
+        bc = np.ascontiguousarray(bc, np.int32)
+        _check(lib().dfk_hops_build(self._ctx, _p(bc), C.c_int(1 if one_good else 0)))
+        return self.hops_stats()
+
+    def hops_build_bci(self, bci, one_good=False):
+        """dfk_hops_build_bci: the same from the barcode index (as read from .bci)."""
+        bci = np.ascontiguousarray(bci, np.int64)
+        _check(lib().dfk_hops_build_bci(self._ctx, _p(bci), C.c_uint64(len(bci)), C.c_int(1 if one_good else 0)))
+        return self.hops_stats()
+
+    def hops_stats(self):
+        """dfk_hops_stats: {counter: value} -- pairs per method and in all, edges searched / extended / decided on the host, times."""
+        out = (C.c_uint64 * HOPS_WORDS)()
+        _check(lib().dfk_hops_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(HOPS)}
+
+    def hops_fetch(self):
+        """dfk_hops_fetch: the sorted pairs, int32[n, 2]."""
+        n = C.c_uint64()
+        _check(lib().dfk_hops_fetch(self._ctx, None, C.c_uint64(0), C.byref(n)))
+        out = np.zeros((n.value, 2), np.int32)
+        _check(lib().dfk_hops_fetch(self._ctx, _p(out), C.c_uint64(n.value), C.byref(n)))
+        return out
+
+    def hops_write(self, path):
+        """a.hops (FindEdgePairs); returns (pairs, (sum, xor) digest of the pairs).  None = no file."""
+        n = C.c_uint64(); dg = (C.c_uint64 * 2)()
+        _check(lib().dfk_hops_write(self._ctx, None if path is None else path.encode(), C.byref(n), dg))
         return n.value, (int(dg[0]), int(dg[1]))
 
     def paths_digest(self):
