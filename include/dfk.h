@@ -316,6 +316,13 @@ int dfk_bads_write_part(dfk_ctx* ctx, const char* path, uint64_t first_pair, uin
  *                       device memory when it returns; the sorted pairs stay in host memory.  Negative barcodes and an odd
  *                       number of reads are DFK_E_ARG.
  *   dfk_hops_build_bci  the same from the barcode index
+ *   dfk_hops_build_arrays  the same stage on a graph and paths given as host arrays, for tests that choose their graph: per edge
+ *                       kmers / inv / to_left / to_right (an edge and its involution of one length), the paths as a CSR
+ *                       (first[n_reads + 1], edges), one barcode and one MarkBads sum (bad: > 150 on either read of a pair) per read,
+ *                       reads_per_batch reads to a batch of paths (0 = one batch).  It lays the paths out as dfk_paths_build does
+ *                       and runs what dfk_hops_build runs, with the context's K; needs no count, graph or paths on the context
+ *                       and leaves those it has alone.  inv that is no involution, an edge or vertex out of range: DFK_E_ARG.
+ *                       Its result is what dfk_hops_stats / _fetch / _write serve until the next dfk_hops_build*.
  *   dfk_hops_stats      out[DFK_HOPS_WORDS]: the counters below
  *   dfk_hops_fetch      the pairs, two int32 each, sorted; pairs NULL and cap 0 = the count alone
  *   dfk_hops_write      a.hops ("BINWRITE" | u64 n | n x (i32, i32)); path NULL = everything but the file; digest (or NULL) = sum
@@ -341,6 +348,9 @@ int dfk_bads_write_part(dfk_ctx* ctx, const char* path, uint64_t first_pair, uin
 #define DFK_HOPS_RANGES 14
 int dfk_hops_build(dfk_ctx* ctx, const int32_t* bc /* [n_reads], host */, int one_good);
 int dfk_hops_build_bci(dfk_ctx* ctx, const int64_t* bci, uint64_t n_bci, int one_good);
+int dfk_hops_build_arrays(dfk_ctx* ctx, uint64_t n_edges, uint64_t n_vertices, const int32_t* kmers, const int32_t* inv, const int32_t* to_left, const int32_t* to_right,
+                          uint64_t n_reads, const uint64_t* first /* [n_reads + 1] */, const int32_t* edges, const int32_t* bc, const uint16_t* sums, int one_good,
+                          uint64_t reads_per_batch);
 int dfk_hops_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_HOPS_WORDS] */);
 int dfk_hops_fetch(dfk_ctx* ctx, int32_t* pairs /* 2 per pair */, uint64_t cap, uint64_t* n_pairs);
 int dfk_hops_write(dfk_ctx* ctx, const char* path /* NULL = all but the file */, uint64_t* n_pairs, uint64_t* digest /* [2] or NULL */);

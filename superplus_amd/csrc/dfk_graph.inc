@@ -37,8 +37,9 @@ struct HostGraph {
     DevBuf d_index, d_recs, d_store; uint64_t index_slots = 0;
     DevBuf d_filter; uint64_t filter_words = 0;                      // the filter in front of the index (dfk_paths_kernels.h), when there was room for it
     struct PathState* paths = nullptr;                               // dfk_paths.inc
+    struct PathState* hops_arrays = nullptr;                         // dfk_hops_build_arrays' result, nothing else in it (dfk_hops.inc)
     void (*paths_free)(struct PathState*) = nullptr;
-    ~HostGraph() { if (paths && paths_free) paths_free(paths); }
+    ~HostGraph() { if (paths && paths_free) paths_free(paths); if (hops_arrays && paths_free) paths_free(hops_arrays); }
 };
 
 inline uint32_t base_at(const uint8_t* p, uint64_t i) { return (p[i >> 2] >> (2 * (i & 3))) & 3u; }
@@ -78,6 +79,30 @@ inline u128h kmer_rc_h(u128h x, uint32_t k)
 struct VKey { uint64_t a, b; bool operator==(const VKey& o) const { return a == o.a && b == o.b; } };
 inline VKey vkey_of(u128h x) { return VKey{(uint64_t)x, (uint64_t)(x >> 64)}; }
 inline uint64_t vkey_hash(const VKey& k) { uint64_t h = k.a * 0x9E3779B97F4A7C15ull ^ (k.b + 0x7F4A7C159E3779B9ull) * 0xC2B2AE3D27D4EB4Full; return h ^ (h >> 29); }
+
+// digraphE::AddEdge keeps from[v] sorted by the vertex it leads to, an equal one behind those already there: (w, edge
+// number) ascending.  Rows by counting, then each (they are a handful long) by insertion.  From G.he and G.n_vertices.
+void graph_rows(HostGraph& G)
+{
+    const size_t nH = G.he.size(), nV = (size_t)G.n_vertices;
+    auto rows = [&](bool out, std::vector<uint32_t>& start, std::vector<int32_t>& nb, std::vector<int32_t>& eid) {
+        start.assign(nV + 1, 0);
+        for (const HostGraph::HEdge& e : G.he) ++start[(out ? e.v : e.w) + 1];
+        for (size_t v = 0; v < nV; ++v) start[v + 1] += start[v];
+        nb.resize(nH); eid.resize(nH);
+        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+        for (size_t i = 0; i < nH; ++i) {                             // in edge-number order: equal neighbours stay in it
+            const HostGraph::HEdge& e = G.he[i];
+            const uint32_t row = (uint32_t)(out ? e.v : e.w), lo = start[row];
+            const int32_t other = out ? e.w : e.v;
+            uint32_t at = fill[row]++;
+            while (at > lo && nb[at - 1] > other) { nb[at] = nb[at - 1]; eid[at] = eid[at - 1]; --at; }
+            nb[at] = other; eid[at] = (int32_t)i;
+        }
+    };
+    rows(true, G.from_start, G.from_v, G.from_e);
+    rows(false, G.to_start, G.to_v, G.to_e);
+}
 
 // buildHBVFromEdges (HBVFromEdges.cc:244-296).  The numbering is the reference's queue order, so it is one thread's work; it
 // is kept to a few hundred nanoseconds an edge (flat tables, no allocation per edge or vertex) because a real genome has a
@@ -185,26 +210,7 @@ void build_hbv(HostGraph& G)
         }
     if ((size_t)next_v != nV) throw std::runtime_error("graph numbering did not reach every vertex");
     G.n_vertices = nV;
-    // digraphE::AddEdge keeps from[v] sorted by the vertex it leads to, an equal one behind those already there: (w, edge
-    // number) ascending.  Rows by counting, then each (they are a handful long) by insertion.
-    const size_t nH = G.he.size();
-    auto rows = [&](bool out, std::vector<uint32_t>& start, std::vector<int32_t>& nb, std::vector<int32_t>& eid) {
-        start.assign(nV + 1, 0);
-        for (const HostGraph::HEdge& e : G.he) ++start[(out ? e.v : e.w) + 1];
-        for (size_t v = 0; v < nV; ++v) start[v + 1] += start[v];
-        nb.resize(nH); eid.resize(nH);
-        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-        for (size_t i = 0; i < nH; ++i) {                             // in edge-number order: equal neighbours stay in it
-            const HostGraph::HEdge& e = G.he[i];
-            const uint32_t row = (uint32_t)(out ? e.v : e.w), lo = start[row];
-            const int32_t other = out ? e.w : e.v;
-            uint32_t at = fill[row]++;
-            while (at > lo && nb[at - 1] > other) { nb[at] = nb[at - 1]; eid[at] = eid[at - 1]; --at; }
-            nb[at] = other; eid[at] = (int32_t)i;
-        }
-    };
-    rows(true, G.from_start, G.from_v, G.from_e);
-    rows(false, G.to_start, G.to_v, G.to_e);
+    graph_rows(G);
     G.built = true;
 }
 

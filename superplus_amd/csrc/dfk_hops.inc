@@ -20,8 +20,16 @@ int hops_of(dfk_ctx* c, PathState** out)
     return 0;
 }
 
+void hops_drop_arrays(dfk_ctx* c)
+{
+    HostGraph* G = graph_of(c);
+    if (G->hops_arrays) { path_state_free(G->hops_arrays); G->hops_arrays = nullptr; }
+}
+
+// the latest build's result: dfk_hops_build_arrays keeps its own beside the graph until the next build of either kind
 int hops_result_of(dfk_ctx* c, PathState** out)
 {
+    if (c && (c->cfg.flags & DFK_F_MARK_BADS) && c->graph_state && graph_of(c)->hops_arrays) { *out = graph_of(c)->hops_arrays; return 0; }
     if (int rc = hops_of(c, out)) return rc;
     if (!(*out)->hops_valid) return fail(DFK_E_STATE, "no edge pairs: call dfk_hops_build");
     return 0;
@@ -186,6 +194,7 @@ int hops_build(dfk_ctx* c, HostGraph* G, PathState* P, const int32_t* bc, const 
                 HIP_TRY(hipGetLastError());
                 ms_mates += tm.stop();
                 uint64_t out_cap = std::max<uint64_t>(4096, n_r / 4);
+                if (const char* e = getenv("DFK_HOPS_OUT_CAP")) out_cap = std::max<uint64_t>(1, (uint64_t)atoll(e));    // (tests: the second attempt)
                 uint64_t h_ctr[HC_N] = {};
                 for (int attempt = 0;; ++attempt) {
                     if ((rc = c->alloc(out, out_cap * 12, "edge pairs found", Place::Low))) return rc;
@@ -282,6 +291,7 @@ int dfk_hops_build(dfk_ctx* c, const int32_t* bc, int one_good)
     if (int rc = hops_of(c, &P)) return rc;
     if (!bc && P->n_reads) return fail(DFK_E_ARG, "null barcode vector");
     HIP_TRY(hipSetDevice(c->device));
+    hops_drop_arrays(c);
     return hops_build(c, graph_of(c), P, bc, nullptr, 0, one_good);
     });
 }
@@ -293,7 +303,88 @@ int dfk_hops_build_bci(dfk_ctx* c, const int64_t* bci, uint64_t n_bci, int one_g
     if (int rc = hops_of(c, &P)) return rc;
     if (!bci) return fail(DFK_E_ARG, "null barcode index");
     HIP_TRY(hipSetDevice(c->device));
+    hops_drop_arrays(c);
     return hops_build(c, graph_of(c), P, nullptr, bci, n_bci, one_good);
+    });
+}
+
+// The stage on a graph and paths given as host arrays: a HostGraph and a PathState made for the call (the batches laid out as
+// k_path_emit leaves them: two header words, offset and lastSkip, before a read's edges, elem_off in bytes; an unplaced read is its
+// two zero words alone), then hops_build() as dfk_hops_build calls it.
+int dfk_hops_build_arrays(dfk_ctx* c, uint64_t n_edges, uint64_t n_vertices, const int32_t* kmers, const int32_t* inv, const int32_t* to_left, const int32_t* to_right,
+                          uint64_t n_reads, const uint64_t* first, const int32_t* edges, const int32_t* bc, const uint16_t* sums, int one_good, uint64_t reads_per_batch)
+{
+    return guarded([&]() -> int {
+    if (!c) return fail(DFK_E_ARG, "null context");
+    if (!(c->cfg.flags & DFK_F_MARK_BADS)) return fail(DFK_E_STATE, "no edge pairs: the context was created without DFK_F_MARK_BADS (FindEdgePairs takes MarkBads' marks)");
+    const uint64_t E = n_edges, N = n_reads;
+    if ((E && (!kmers || !inv || !to_left || !to_right)) || !first || (N && (!bc || !sums))) return fail(DFK_E_ARG, "null argument");
+    if (N % 2) return fail(DFK_E_ARG, "%llu reads: FindEdgePairs works on pairs", (unsigned long long)N);
+    if (N >= (1ull << 31) || E >= (1ull << 31) || n_vertices >= (1ull << 31)) return fail(DFK_E_ARG, "%llu reads, %llu edges, %llu vertices: 2^31 - 1 of each at most", (unsigned long long)N, (unsigned long long)E, (unsigned long long)n_vertices);
+    for (uint64_t e = 0; e < E; ++e) {
+        if (inv[e] < 0 || (uint64_t)inv[e] >= E || inv[inv[e]] != (int32_t)e) return fail(DFK_E_ARG, "inv is not an involution at edge %llu", (unsigned long long)e);
+        if (kmers[e] < 1 || kmers[inv[e]] != kmers[e]) return fail(DFK_E_ARG, "edge %llu has %d k-mers, its involution %d", (unsigned long long)e, kmers[e], kmers[inv[e]]);
+        if (to_left[e] < 0 || (uint64_t)to_left[e] >= n_vertices || to_right[e] < 0 || (uint64_t)to_right[e] >= n_vertices) return fail(DFK_E_ARG, "edge %llu joins a vertex out of range", (unsigned long long)e);
+    }
+    if (first[0] != 0) return fail(DFK_E_ARG, "the paths do not start at 0");
+    for (uint64_t i = 0; i < N; ++i) {
+        if (first[i + 1] < first[i]) return fail(DFK_E_ARG, "the paths' starts fall at read %llu", (unsigned long long)i);
+        if (bc[i] < 0) return fail(DFK_E_ARG, "read %llu has barcode %d: barcodes are not negative", (unsigned long long)i, bc[i]);
+    }
+    if (first[N] && !edges) return fail(DFK_E_ARG, "null argument");
+    for (uint64_t k = 0; k < first[N]; ++k) if (edges[k] < 0 || (uint64_t)edges[k] >= E) return fail(DFK_E_ARG, "a path holds edge %d: the graph has %llu", edges[k], (unsigned long long)E);
+    HIP_TRY(hipSetDevice(c->device));
+    hops_drop_arrays(c);
+    // the graph: a canonical edge per edge and its involution, the smaller number its forward orientation
+    HostGraph G;
+    G.K = c->cfg.K; G.n_vertices = n_vertices; G.he.resize(E);
+    for (uint64_t e = 0; e < E; ++e) {
+        if ((uint64_t)inv[e] < e) continue;
+        const uint32_t ce = (uint32_t)G.ce.size();
+        G.ce.push_back(GraphEdge{(uint32_t)kmers[e], 0}); G.fwd.push_back((int32_t)e); G.rev.push_back(inv[e]);
+        G.he[e] = HostGraph::HEdge{ce, 0, to_left[e], to_right[e]};
+        if ((uint64_t)inv[e] != e) G.he[inv[e]] = HostGraph::HEdge{ce, 1, to_left[inv[e]], to_right[inv[e]]};
+    }
+    graph_rows(G);
+    G.built = true;
+    // the paths
+    PathState* P = new PathState;
+    P->c = c;
+    struct Holder { dfk_ctx* c; PathState* P; ~Holder() { if (P) path_state_free(P); } } holder{c, P};
+    const uint64_t mark = c->alloc_seq;
+    const uint64_t per = reads_per_batch ? reads_per_batch : std::max<uint64_t>(1, N);
+    auto body = [&]() -> int {
+        int rc;
+        for (uint64_t r0 = 0; r0 < N; r0 += per) {
+            PathBatch B; B.r0 = r0; B.n = std::min(per, N - r0); B.file_base = 24 + 8 * r0 + 4 * first[r0];
+            std::vector<uint32_t> var, off(B.n);
+            for (uint64_t i = 0; i < B.n; ++i) {
+                off[i] = (uint32_t)(var.size() * 4);
+                var.push_back(0u); var.push_back(0u);
+                for (uint64_t k = first[r0 + i]; k < first[r0 + i + 1]; ++k) var.push_back((uint32_t)edges[k]);
+            }
+            B.var_bytes = var.size() * 4;
+            if (B.var_bytes >= (1ull << 32)) return fail(DFK_E_ARG, "a batch of %llu reads holds %llu bytes of paths: its offsets keep 32 bits", (unsigned long long)B.n, (unsigned long long)B.var_bytes);
+            if ((rc = upload_vec(c, B.var, var, "a.paths data")) || (rc = upload_vec(c, B.elem_off, off, "a.paths offsets"))) return rc;
+            P->batches.push_back(B);
+        }
+        if ((rc = c->alloc(P->bad_sums, std::max<uint64_t>(1, N) * 2, "bad-base sums"))) return rc;
+        if (N) HIP_TRY(hipMemcpy(P->bad_sums.p, sums, N * 2, hipMemcpyHostToDevice));
+        P->n_reads = N; P->n_edges = first[N]; P->built = true;
+        for (uint64_t i = 0; i < N; ++i) P->n_placed += first[i + 1] > first[i];
+        return hops_build(c, &G, P, bc, nullptr, 0, one_good);
+    };
+    int rc;
+    try { rc = body(); } catch (const std::runtime_error& e) { rc = fail(DFK_E_HIP, "%s", e.what()); }
+    (void)hipStreamSynchronize(c->stream);
+    c->release_since(mark);                                                  // the batches, the sums, the graph's tables
+    P->batches.clear(); P->built = false; P->tables = false;
+    P->bad_sums = P->xlat = P->he_ce = P->he_left = P->he_right = P->from_start = P->from_vtx = P->from_edge = P->to_start = P->to_vtx = P->to_edge = DevBuf{};
+    if (rc) return rc;
+    holder.P = nullptr;
+    graph_of(c)->hops_arrays = P;                                            // hops, hops_stats and hops_valid are what is left in it
+    graph_of(c)->paths_free = path_state_free;
+    return 0;
     });
 }
 

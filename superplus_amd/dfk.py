@@ -31,7 +31,7 @@ EXPORTS = [
     "dfk_paths_digest", "dfk_paths_verify", "dfk_paths_verify_device", "dfk_pbf_run", "dfk_pbf_result", "dfk_pbf_free",
     "dfk_paths_var_bytes", "dfk_paths_write_part", "dfk_shard_pidx_pairs", "dfk_shard_pidx_write", "dfk_shard_dup_keys", "dfk_shard_dup_answer", "dfk_shard_dup_write",
     "dfk_bads_sums", "dfk_bads_write", "dfk_bads_write_part",
-    "dfk_hops_build", "dfk_hops_build_bci", "dfk_hops_stats", "dfk_hops_fetch", "dfk_hops_write",
+    "dfk_hops_build", "dfk_hops_build_bci", "dfk_hops_build_arrays", "dfk_hops_stats", "dfk_hops_fetch", "dfk_hops_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -305,6 +305,20 @@ class Dfk:
         """dfk_hops_build_bci: the same from the barcode index (as read from .bci)."""
         bci = np.ascontiguousarray(bci, np.int64)
         _check(lib().dfk_hops_build_bci(self._ctx, _p(bci), C.c_uint64(len(bci)), C.c_int(1 if one_good else 0)))
+        return self.hops_stats()
+
+    def hops_build_arrays(self, kmers, inv, to_left, to_right, n_vertices, paths, bc, sums, one_good=False, reads_per_batch=0):
+        """dfk_hops_build_arrays: the same stage on a graph and paths given as arrays (paths: a list of edge lists, one per read; sums:
+        MarkBads' per-read sums, u16); reads_per_batch 0 = one batch.  Returns hops_stats()."""
+        kmers, inv, to_left, to_right, bc = (np.ascontiguousarray(a, np.int32) for a in (kmers, inv, to_left, to_right, bc))
+        sums = np.ascontiguousarray(sums, np.uint16)
+        first = np.zeros(len(paths) + 1, np.uint64)
+        first[1:] = np.cumsum([len(p) for p in paths], dtype=np.uint64)
+        edges = np.ascontiguousarray([e for p in paths for e in p] or [0], np.int32)
+        assert len(inv) == len(to_left) == len(to_right) == len(kmers) and len(bc) == len(sums) == len(paths)
+        _check(lib().dfk_hops_build_arrays(self._ctx, C.c_uint64(len(kmers)), C.c_uint64(n_vertices), _p(kmers), _p(inv), _p(to_left), _p(to_right),
+                                           C.c_uint64(len(paths)), _p(first), _p(edges), _p(bc), _p(sums), C.c_int(1 if one_good else 0),
+                                           C.c_uint64(reads_per_batch)))
         return self.hops_stats()
 
     def hops_stats(self):

@@ -1,5 +1,5 @@
 // tests/cpp/test_hops.cc -- superplus_amd/csrc/dfk_hops.h (FindEdgePairs, 10X/Closomatic.cc:17-358, restated in C++) on the host:
-// a graph and three searches worked out by hand, then the six seeded graphs of tests/hops_cases.py against what tests/hops_oracle.py said about them
+// a graph and three searches worked out by hand, then the seeded graphs of tests/hops_cases.py (dense random ones, gapped chains) against what tests/hops_oracle.py said about them
 // (tests/cpp/hops_cases.txt).  Built plain and under -fsanitize=address,undefined by tests/test_hops_cpu.py.
 //   g++ -std=c++17 -O1 -g -I superplus_amd/csrc -o test_hops tests/cpp/test_hops.cc && ./test_hops tests/cpp/hops_cases.txt
 #include "dfk_hops.h"
