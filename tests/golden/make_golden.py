@@ -9,6 +9,7 @@ restated; see oracle/ref_driver.cc).  Only data is committed: no reference sourc
 
   python tests/golden/make_golden.py        (needs oracle/_ref/refdrv: oracle/build_ref.sh)
   python tests/golden/make_golden.py pbf_ref    (tests/golden/pbf_ref.json alone)
+  python tests/golden/make_golden.py zoo        (tests/golden/zoo.*, graph_zoo_k*/ and expect_zoo_k*.npz alone)
 """
 import os
 import struct
@@ -406,7 +407,28 @@ def main():
     np.savez_compressed(os.path.join(HERE, "expect_frag_k48.npz"), solid_post=post)
     assert ne >= 870
     print("graph frag: solid", len(post), "HBV edges", ne)
+    zoo()
     pbf_ref()
+
+
+def zoo():
+    """Degenerate topology at every K (tests/zoo_synth.py: circles of many lengths, reverse-complement-symmetric repeats, loops on a
+    branching vertex, tandem repeats, a diploid stretch of more than 870 edges): the one read set through the reference's classes at
+    K = 40, 48 and 60, with every file the frag fixture has."""
+    from superplus_amd import feudal
+    from tests.zoo_synth import ZOO_SEED, make_zoo
+    reads, quals, bci = make_zoo(ZOO_SEED)
+    raw = os.path.join(HERE, "zoo.raw")
+    write_raw(raw, reads, quals)
+    zo = os.path.join(HERE, "zoo")
+    subprocess.check_call([REFDRV, "mkreads", raw, zo], stdout=subprocess.DEVNULL)
+    os.remove(raw)
+    feudal.write_bci(zo + ".bci", bci)
+    for K in (40, 48, 60):
+        post, ne = run_graph(zo, os.path.join(HERE, f"tmp_gzoo{K}"), K, 1, 2, 3, os.path.join(HERE, f"graph_zoo_k{K}"), extra=("a.paths.inv", "a.countsb", "a.dup"))
+        np.savez_compressed(os.path.join(HERE, f"expect_zoo_k{K}.npz"), solid_post=post)
+        assert ne > 870
+        print(f"graph zoo K={K}: solid", len(post), "HBV edges", ne)
 
 
 # The seeded inputs the ParseBarcodedFastqs tests compare with the reference's binary (tests/test_parse_barcoded_fastqs.py,
@@ -442,4 +464,4 @@ def pbf_ref():
 
 
 if __name__ == "__main__":
-    pbf_ref() if sys.argv[1:] == ["pbf_ref"] else main()
+    pbf_ref() if sys.argv[1:] == ["pbf_ref"] else zoo() if sys.argv[1:] == ["zoo"] else main()

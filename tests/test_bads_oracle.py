@@ -15,7 +15,11 @@ TABLE = [("graph_pathy2_k48", 48, "pathy2", 23400, 18556, 13768, 1309, None, 2, 
          ("graph_frag_k48", 48, "frag", 6000, 5634, 1854, 0, 111, 0, 3231, 702, 1046),
          ("graph_k48", 48, "reads", 1800, 1215, 505, 6, 1437, 0, 8, 153, 334),
          ("graph_k40_nobc", 40, "reads", 1800, 1409, 693, 8, 1847, 0, 33, 88, 208),
-         ("graph_k60_nobc", 60, "reads", 1800, 771, 271, 0, 120, 0, 3, 196, 348)]
+         ("graph_k60_nobc", 60, "reads", 1800, 771, 271, 0, 120, 0, 3, 196, 348),
+         # the zoo (tests/zoo_synth.py): a tenth of its reads carry one to three substitutions of quality 30 to 60
+         ("graph_zoo_k40", 40, "zoo", 20624, 20461, 2129, 285, 3060, 80, 14504, 176, 2432),
+         ("graph_zoo_k48", 48, "zoo", 20624, 20170, 1820, 234, 2820, 54, 13264, 154, 2260),
+         ("graph_zoo_k60", 60, "zoo", 20624, 19566, 1196, 159, 1920, 25, 8021, 90, 1796)]
 
 _cache = {}
 

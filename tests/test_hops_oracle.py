@@ -17,6 +17,12 @@ TABLE = [("graph_pathy2_k48", 48, "pathy2", 3184, 23400, (69, 62, 667, 725), (25
          ("graph_k48", 48, "reads", 262, 1800, (48, 0, 48, 48), (48, 0, 48, 48), 88, 0, 2, 38, 3, 3, 3),
          ("graph_k40_nobc", 40, "reads", 146, 1800, (109, 2, 133, 138), (136, 0, 133, 138), 62, 5, 0, 39, 4, 3, 3),
          ("graph_k60_nobc", 60, "reads", 312, 1800, (2, 0, 2, 2), (2, 0, 2, 2), 62, 0, 0, 10, 1, 2, 1)]
+# the zoo (tests/zoo_synth.py) in rows of its own: reads that go round a short cycle name one edge dozens of times, so the members of
+# an X are longer and the searches wider than the device's default LDS capacities hold (tests/test_gpu_hops.py asserts of every row
+# of TABLE that they do); tests/test_gpu_zoo.py runs these and says how many edges the host must decide
+ZOO_TABLE = [("graph_zoo_k40", 40, "zoo", 1346, 20624, (0, 0, 344, 344), (1, 0, 344, 345), 466, 396, 3, 38, 55, 37, 39),
+             ("graph_zoo_k48", 48, "zoo", 1334, 20624, (0, 0, 465, 465), (2, 0, 465, 467), 354, 258, 2, 28, 54, 30, 59),
+             ("graph_zoo_k60", 60, "zoo", 1054, 20624, (0, 0, 349, 349), (0, 0, 349, 349), 382, 287, 2, 25, 33, 22, 43)]
 SPECIAL = ("graph_special_k48", 48, "special")
 HOT = ("graph_hot_k48_minfreq2", 48, "hot")               # gives no pairs: the empty case
 
@@ -212,7 +218,7 @@ def test_search_rounds_and_an_overlap_mismatch_before_l():
     assert hops_oracle.search(0, X, kmers)[:2] == (True, 1)      # [e0, e1, e2] is a member already (80), + [e2, e3] -> 120
 
 
-@pytest.mark.parametrize("row", TABLE, ids=[r[0] for r in TABLE])
+@pytest.mark.parametrize("row", TABLE + ZOO_TABLE, ids=[r[0] for r in TABLE + ZOO_TABLE])
 def test_restatement_gives_the_counts_of_the_fixtures(golden_dir, row):
     case, K, which, E, N, plain, one_good, searched, extended, rounds, largest_x, largest_exts, longest, longest_ext = row
     i = fixture_inputs(golden_dir, case, K, which)

@@ -15,7 +15,8 @@ from tests.test_oracle_golden import load_hot, load_inputs
 CASES = [("graph_k48", 48, "expect_k48.npz", "reads"), ("graph_k40_nobc", 40, "expect_k40_nobc.npz", "reads"),
          ("graph_k60_nobc", 60, "expect_k60_nobc.npz", "reads"), ("graph_hot_k48_minfreq2", 48, "expect_hot_k48_minfreq2.npz", "hot"),
          ("graph_special_k48", 48, "expect_special_k48_nobc.npz", "special"), ("graph_pathy_k48", 48, "expect_pathy_k48.npz", "pathy"),
-         ("graph_frag_k48", 48, "expect_frag_k48.npz", "frag"), ("graph_pathy2_k48", 48, "expect_pathy2_k48.npz", "pathy2")]
+         ("graph_frag_k48", 48, "expect_frag_k48.npz", "frag"), ("graph_pathy2_k48", 48, "expect_pathy2_k48.npz", "pathy2")] + \
+        [(f"graph_zoo_k{K}", K, f"expect_zoo_k{K}.npz", "zoo") for K in (40, 48, 60)]
 
 
 def load_named(golden_dir, name):
@@ -98,6 +99,20 @@ def test_paths_index_and_dups_of_the_larger_pather_input(golden_dir):
     files["a.dup"] = paths_oracle.mark_dups(r["paths"], reads, quals)
     for f, b in files.items():
         assert b == open(os.path.join(golden_dir, "graph_pathy2_k48", f), "rb").read(), f
+
+
+@pytest.mark.parametrize("K", [40, 48, 60])
+def test_paths_index_and_dups_of_the_zoo(golden_dir, K):
+    """... and for the zoo (tests/zoo_synth.py) at every K: reads that go round a short cycle stand dozens of times in one edge's list."""
+    solid = np.load(os.path.join(golden_dir, f"expect_zoo_k{K}.npz"))["solid_post"]
+    g = graph_oracle.run(solid, K)
+    reads, quals = paths_oracle.unpack_reads(load_reads(golden_dir, "zoo"))
+    r = paths_oracle.run(reads, quals, g, K)
+    files = paths_oracle.paths_index(r["paths"], g["hbv"].involution())
+    files["a.dup"] = paths_oracle.mark_dups(r["paths"], reads, quals)
+    for f, b in files.items():
+        assert b == open(os.path.join(golden_dir, f"graph_zoo_k{K}", f), "rb").read(), f
+    assert max(max(np.bincount(p)) for _, p in r["paths"] if len(p)) >= 10
 
 
 def test_paths_index_and_dups_match_reference_files(golden_dir):

@@ -20,6 +20,9 @@ EXPECT = {
     "graph_pathy_k48": [3357, 0, 146851, 146029, 0, 3302, 0, 1947],
     "graph_frag_k48": [5634, 0, 232037, 223901, 0, 5277, 0, 15832],
     "graph_pathy2_k48": [18556, 0, 772254, 757058, 0, 17781, 0, 27569],
+    "graph_zoo_k40": [20461, 0, 1159855, 1148731, 0, 20251, 0, 19516],
+    "graph_zoo_k48": [20170, 0, 996227, 987599, 0, 19982, 0, 19339],
+    "graph_zoo_k60": [19566, 0, 762432, 757410, 0, 19421, 0, 14263],
 }
 
 
