@@ -305,20 +305,17 @@ int table_totals(dfk_ctx* c, const DevBuf& acc, uint64_t nb, uint64_t* n_records
 // The counting scan in three steps, so that a caller whose reads are still arriving (count_host: the scan runs under the upload
 // of the bases) can run it a range of reads at a time: begin (tables, zeroed), range (a launch over reads [r0, r1)), end (the
 // overflow list, the totals, the check against the trim's instance count).  partition_count is all three over every read.
-constexpr uint64_t SCAN_TAIL_READS = 32ull << 20;   // the last piece of a keyed scan whose keys are counted under the next scan
+// What the scan decides on the host -- keyed or not, the keys' geometry and scratch sizes, the pieces, grids, LDS -- is
+// the ScanPlan of dfk_scan_plan.h; here are the allocations, launches and events that carry it out.
 struct ScanJob {
-    PartParams pp; uint64_t nb = 0, n_bins = 0, ovf_cap = 0; bool by_class = false, ranged = false;
+    PartParams pp; ScanPlan plan;
     DevBuf ovf_tmp, d_n;
-    // the register scan's run keys (k_scan_count<K, 16, true>): class slices, their partition into sub-slices, and per
-    // sub-slice totals | offsets | cursors -- all scratch, counted a piece of at most piece_reads reads at a time
-    bool keyed = false; uint32_t n_cls = 0, n_sub = 0, sb = 0; uint64_t piece_reads = 0, tail_reads = 0;
-    ScanKeys sk{};
-    DevBuf keys, keys2, fill, sub;
-    // With a second stream the keys of piece i are counted under the scan of piece i + 1: `keys` and `fill` are n_slices = 2
-    // slices, piece i's scan (c->stream) fills slice i % 2, its subcount | offsets | partition follow on c->stream2, and its
-    // k_keys_count -- 128 KB of LDS, no room on a CU that holds scan blocks -- on c->stream behind the next scan.  The pipeline
-    // carries across scan_range calls (the pieces of run_under_upload); the range that ends the reads, and scan_end, drain it.
-    uint32_t n_slices = 1; uint64_t n_pieces = 0; bool count_due = false;
+    DevBuf keys, keys2, fill, sub;        // the run keys' scratch (ScanPlan)
+    // With a second stream piece i's scan (c->stream) fills slice i % 2, its subcount | offsets | partition follow on
+    // c->stream2, and its k_keys_count -- 128 KB of LDS, no room on a CU that holds scan blocks -- on c->stream behind the
+    // next scan.  The pipeline carries across scan_range calls (the pieces of run_under_upload); the range that ends the
+    // reads, and scan_end, drain it.
+    uint64_t n_pieces = 0; bool count_due = false;
     hipEvent_t ev_scan = nullptr, ev_count = nullptr, ev_part[2] = {nullptr, nullptr};   // last scan | last k_keys_count | last partition of a slice
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;                  // a pair per launch: ms_part_count is their sum
     ~ScanJob()
@@ -331,59 +328,43 @@ struct ScanJob {
 // (the register scan takes ranges; the general scan -- other minimizer lengths -- only everything at once)
 template <int K> bool scan_takes_ranges(const dfk_ctx* c) { return c->cfg.minimizer_len == 16; }
 
+// the scan's switches: DFK_SCAN_BLOCKS once per process, the others at every scan (tests switch them within one process)
+ScanSwitches scan_switches()
+{
+    static const uint32_t scan_blocks = getenv("DFK_SCAN_BLOCKS") ? (uint32_t)atoi(getenv("DFK_SCAN_BLOCKS")) : 0;
+    ScanSwitches sw;
+    sw.scan_blocks = scan_blocks;
+    if (const char* e = getenv("DFK_SCAN_KEY_PIECE")) { sw.key_piece_set = true; sw.key_piece = strtoull(e, nullptr, 10); }
+    if (const char* e = getenv("DFK_SCAN_KEY_TAIL")) sw.key_tail = strtoull(e, nullptr, 10);
+    sw.no_overlap = getenv("DFK_NO_OVERLAP") != nullptr;
+    return sw;
+}
+
 template <int K>
 int scan_begin(dfk_ctx* c, const Inputs& in, uint32_t log2_world, int64_t read_id0, BucketTable* T, bool by_class, ScanJob* J)
 {
     J->pp = part_params<K>(c, T->log2_nb, log2_world, read_id0, 0, 1u << (T->log2_nb - log2_world));
-    J->nb = 1ull << T->log2_nb; J->by_class = by_class;
+    J->plan = plan_scan(ScanInputs{K, J->pp.W, T->log2_nb, log2_world, in.n_reads, in.packed_bytes, by_class, scan_takes_ranges<K>(c), c->stream2 != nullptr, scan_switches()});
+    ScanPlan& P = J->plan;
     int rc = 0;
-    J->n_bins = 2ull * (PART_CLASSES << log2_world);
-    if (by_class) { rc = c->alloc(T->class_hist, J->n_bins * 8, "class counters", Place::Low); if (rc) return rc; HIP_TRY(hipMemsetAsync(T->class_hist.p, 0, J->n_bins * 8, c->stream)); }
-    else { rc = c->alloc(T->acc, J->nb * 8, "bucket counters", Place::Low); if (rc) return rc; }
+    if (by_class) { rc = c->alloc(T->class_hist, P.n_bins * 8, "class counters", Place::Low); if (rc) return rc; HIP_TRY(hipMemsetAsync(T->class_hist.p, 0, P.n_bins * 8, c->stream)); }
+    else { rc = c->alloc(T->acc, P.nb * 8, "bucket counters", Place::Low); if (rc) return rc; }
     rc = c->alloc(T->summ, std::max<uint64_t>(1, in.n_reads) * 16, "run summaries", Place::Low); if (rc) return rc;
     rc = c->alloc(T->classes, std::max<uint64_t>(1, in.n_reads) * 4, "read bucket classes", Place::Low); if (rc) return rc;
-    if (!by_class) HIP_TRY(hipMemsetAsync(T->acc.p, 0, J->nb * 8, c->stream));
-    // reads whose runs do not fit a summary are listed by the scan itself (two in 10^5 at 2x100 bp); if the list
-    // outgrows the room set aside for it the summaries are searched instead
-    J->ovf_cap = in.n_reads / 16 + 1024;
-    rc = c->alloc(J->ovf_tmp, J->ovf_cap * 4, "overflow read list (scratch)"); if (rc) return rc;
+    if (!by_class) HIP_TRY(hipMemsetAsync(T->acc.p, 0, P.nb * 8, c->stream));
+    rc = c->alloc(J->ovf_tmp, P.ovf_cap * 4, "overflow read list (scratch)"); if (rc) return rc;
     rc = c->alloc(J->d_n, 16, "overflow read count"); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(J->d_n.p, 0, 16, c->stream));
-    // keys a read makes: its first run and about two per W + 1 k-mers (random minimizers).  The keys pay where that is
-    // four or more (at 2 x 100 bp: K=40, 5.7 runs a read, the scan 505 -> 409 ms; K=48, 4.1, 368 -> 333); at K=60 (2.8)
-    // the counting kernels cost more than the atomics they replace (284 -> 313 ms), and the scan keeps its atomics
-    const double runs = in.n_reads ? 1.0 + 2.0 * std::max(0.0, 4.0 * (double)in.packed_bytes / (double)in.n_reads - K + 1) / (J->pp.W + 1) : 0.0;
-    J->keyed = !by_class && scan_takes_ranges<K>(c) && in.n_reads && (runs >= 3.5 || getenv("DFK_SCAN_KEY_PIECE"));
-    if (J->keyed) {
-        const uint32_t lb = T->log2_nb, cb = std::min<uint32_t>(6, lb);
-        J->sk.ib = lb - cb; J->n_cls = 1u << cb;
-        J->sb = std::min(KEY_SUB_BITS, J->sk.ib); J->n_sub = 1u << (J->sk.ib - J->sb);
-        // a quarter to spare for reads longer than the mean and classes fuller than the mean (what still does not fit is
-        // counted by the global atomic)
-        const double per_read = 1.25 * runs;
-        // the keys' copies (a piece's slices, or two pieces' when they are counted under the next scan; their partition); at
-        // most a third of what the arena can still give, and never more than KEY_SCRATCH_MAX, so that the pass plan after
-        // scan_end finds the arena as it was
-        constexpr uint64_t KEY_SCRATCH_MAX = 16ull << 30;
-        J->n_slices = c->stream2 && !getenv("DFK_NO_OVERLAP") ? 2 : 1;
-        const uint32_t copies = J->n_slices + 1;
-        const uint64_t want = 4ull * copies * (uint64_t)(per_read * (double)in.n_reads) + 4ull * copies * J->n_cls;
-        const uint64_t room = std::min<uint64_t>(std::min(want, KEY_SCRATCH_MAX), c->largest_allocatable() / 3);
-        J->sk.cap = std::max<uint64_t>(1024, room / (4 * copies) / J->n_cls) & ~3ull;   // (16-byte loads of the slices)
-        J->piece_reads = std::max<uint64_t>(PART_THREADS, (uint64_t)((double)(J->sk.cap * J->n_cls) / per_read));
-        if (const char* e = getenv("DFK_SCAN_KEY_PIECE")) J->piece_reads = std::max<uint64_t>(1, std::min<uint64_t>(J->piece_reads, strtoull(e, nullptr, 10)));
-        // the last piece's keys have no scan to be counted under: the pieces halve towards the end of the reads, down to
-        // tail_reads (profiles/r07_scan_overlap.txt: flat from 0 to 64 M reads; every extra piece is a k_keys_count launch)
-        J->tail_reads = getenv("DFK_SCAN_KEY_TAIL") ? strtoull(getenv("DFK_SCAN_KEY_TAIL"), nullptr, 10) : SCAN_TAIL_READS;
-        const uint64_t n_subs = (uint64_t)J->n_cls * J->n_sub;
-        rc = c->alloc(J->keys, J->n_slices * J->sk.cap * J->n_cls * 4, "run keys (scratch)"); if (rc) return rc;
-        rc = c->alloc(J->keys2, J->sk.cap * J->n_cls * 4, "run keys by sub-slice (scratch)"); if (rc) return rc;
-        rc = c->alloc(J->fill, J->n_slices * J->n_cls * 8, "run key slice fills (scratch)"); if (rc) return rc;
-        rc = c->alloc(J->sub, (3 * n_subs + 1) * 8, "run key sub-slices (scratch)"); if (rc) return rc;
-        if (J->n_slices > 1)
+    if (P.keyed) {
+        size_scan_keys(P, c->largest_allocatable());
+        rc = c->alloc(J->keys, P.keys_bytes, "run keys (scratch)"); if (rc) return rc;
+        rc = c->alloc(J->keys2, P.keys2_bytes, "run keys by sub-slice (scratch)"); if (rc) return rc;
+        rc = c->alloc(J->fill, P.fill_bytes, "run key slice fills (scratch)"); if (rc) return rc;
+        rc = c->alloc(J->sub, P.sub_bytes, "run key sub-slices (scratch)"); if (rc) return rc;
+        if (P.n_slices > 1)
             for (hipEvent_t* e : {&J->ev_scan, &J->ev_count, &J->ev_part[0], &J->ev_part[1]}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        TRACE("run keys: %u x %u classes of %llu keys, %u sub-slices each, pieces of %llu reads", J->n_slices, J->n_cls, (unsigned long long)J->sk.cap,
-              J->n_sub, (unsigned long long)J->piece_reads);
+        TRACE("run keys: %u x %u classes of %llu keys, %u sub-slices each, pieces of %llu reads", P.n_slices, P.n_cls, (unsigned long long)P.cap,
+              P.n_sub, (unsigned long long)P.piece_reads);
     }
     return 0;
 }
@@ -391,13 +372,14 @@ int scan_begin(dfk_ctx* c, const Inputs& in, uint32_t log2_world, int64_t read_i
 // piece i's k_keys_count, queued on c->stream once its partition (c->stream2) is done
 inline int scan_keys_count(dfk_ctx* c, BucketTable* T, ScanJob* J)
 {
-    const uint64_t n_subs = (uint64_t)J->n_cls * J->n_sub;
+    const ScanPlan& P = J->plan;
+    const uint64_t n_subs = P.n_subs();
     const auto* off = (const unsigned long long*)J->sub.p + n_subs;
-    if (J->n_slices > 1) HIP_TRY(hipStreamWaitEvent(c->stream, J->ev_part[(J->n_pieces - 1) & 1], 0));
+    if (P.n_slices > 1) HIP_TRY(hipStreamWaitEvent(c->stream, J->ev_part[scan_piece_step(P, J->n_pieces - 1).slice], 0));
     hipLaunchKernelGGL(k_keys_count, dim3((unsigned)n_subs), dim3(1024), 0, c->stream,
-                       (const uint32_t*)J->keys2.p, off, J->sb, (unsigned long long*)T->acc.p);
+                       (const uint32_t*)J->keys2.p, off, P.sb, (unsigned long long*)T->acc.p);
     HIP_TRY(hipGetLastError());
-    if (J->n_slices > 1) HIP_TRY(hipEventRecord(J->ev_count, c->stream));
+    if (P.n_slices > 1) HIP_TRY(hipEventRecord(J->ev_count, c->stream));
     J->count_due = false;
     return 0;
 }
@@ -407,25 +389,23 @@ inline int scan_keys_count(dfk_ctx* c, BucketTable* T, ScanJob* J)
 template <int K>
 int scan_keys_piece(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, uint64_t r0, uint64_t r1)
 {
-    static const unsigned scan_blocks = getenv("DFK_SCAN_BLOCKS") ? (unsigned)atoi(getenv("DFK_SCAN_BLOCKS")) : 0;
+    const ScanPlan& P = J->plan;
     const unsigned cus = (unsigned)c->prop.multiProcessorCount;
-    const unsigned grid = (unsigned)std::min<uint64_t>((r1 - r0 + PART_THREADS - 1) / PART_THREADS, (uint64_t)(scan_blocks ? scan_blocks : 128u) * cus);
-    const uint64_t n_subs = (uint64_t)J->n_cls * J->n_sub;
-    const bool two = J->n_slices > 1;
-    const uint32_t sl = two ? (uint32_t)(J->n_pieces & 1) : 0;
+    const unsigned grid = scan_grid(P, r1 - r0, cus);
+    const uint64_t n_subs = P.n_subs();
+    const bool two = P.n_slices > 1;
+    const PieceStep step = scan_piece_step(P, J->n_pieces);
+    const uint32_t sl = step.slice;
     hipStream_t ks = two ? c->stream2 : c->stream;                       // subcount, offsets, partition
     auto* cnt = (unsigned long long*)J->sub.p;
     auto* off = cnt + n_subs;
     auto* cur = off + n_subs + 1;
-    ScanKeys sk = J->sk;
-    sk.keys = (uint32_t*)J->keys.p + (uint64_t)sl * sk.cap * J->n_cls;
-    sk.fill = (unsigned long long*)J->fill.p + (uint64_t)sl * J->n_cls;
-    if (two && J->n_pieces >= 2) HIP_TRY(hipStreamWaitEvent(c->stream, J->ev_part[sl], 0));   // the slice's last reader
-    HIP_TRY(hipMemsetAsync(sk.fill, 0, J->n_cls * 8, c->stream));
-    const size_t lds = SCAN_RUN_LDS + SCAN_STAGE_LDS;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, true>), dim3(grid), dim3(PART_THREADS), lds, c->stream,
+    ScanKeys sk{(uint32_t*)J->keys.p + (uint64_t)sl * P.cap * P.n_cls, (unsigned long long*)J->fill.p + (uint64_t)sl * P.n_cls, P.cap, P.ib};
+    if (step.wait_slice_reader) HIP_TRY(hipStreamWaitEvent(c->stream, J->ev_part[sl], 0));
+    HIP_TRY(hipMemsetAsync(sk.fill, 0, P.n_cls * 8, c->stream));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, true>), dim3(grid), dim3(PART_THREADS), scan_lds(P), c->stream,
                        in.packed, in.packed_bytes, in.base_off, (const uint32_t*)c->good_len.p, r0, r1, J->pp,
-                       (unsigned long long*)T->acc.p, (unsigned long long*)nullptr, (unsigned long long*)J->d_n.p, J->ovf_cap,
+                       (unsigned long long*)T->acc.p, (unsigned long long*)nullptr, (unsigned long long*)J->d_n.p, P.ovf_cap,
                        (uint32_t*)J->ovf_tmp.p, (uint4*)T->summ.p, (uint32_t*)T->classes.p, sk);
     HIP_TRY(hipGetLastError());
     if (two) {
@@ -433,18 +413,18 @@ int scan_keys_piece(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, ui
         // the piece before: its partition has had this scan to run under; its count frees keys2 and the sub-slice tables
         if (J->count_due) { int rc = scan_keys_count(c, T, J); if (rc) return rc; }
         HIP_TRY(hipStreamWaitEvent(ks, J->ev_scan, 0));
-        if (J->n_pieces >= 1) HIP_TRY(hipStreamWaitEvent(ks, J->ev_count, 0));
+        if (step.wait_prev_count) HIP_TRY(hipStreamWaitEvent(ks, J->ev_count, 0));
     }
     HIP_TRY(hipMemsetAsync(cnt, 0, n_subs * 8, ks));
-    const dim3 per_class(std::max(1u, 16u * cus / J->n_cls), J->n_cls);
-    const uint32_t sh = 6 + J->sb;
-    hipLaunchKernelGGL(k_keys_subcount, per_class, dim3(256), J->n_sub * 4, ks,
-                       (const uint32_t*)sk.keys, (const unsigned long long*)sk.fill, sk.cap, sh, J->n_sub, cnt);
+    const dim3 per_class(std::max(1u, 16u * cus / P.n_cls), P.n_cls);
+    const uint32_t sh = 6 + P.sb;
+    hipLaunchKernelGGL(k_keys_subcount, per_class, dim3(256), P.n_sub * 4, ks,
+                       (const uint32_t*)sk.keys, (const unsigned long long*)sk.fill, sk.cap, sh, P.n_sub, cnt);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_keys_offsets, dim3(1), dim3(1024), 0, ks, (const unsigned long long*)cnt, (uint32_t)n_subs, off, cur);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_keys_partition, per_class, dim3(256), J->n_sub * 12, ks,
-                       (const uint32_t*)sk.keys, (const unsigned long long*)sk.fill, sk.cap, sh, J->n_sub, cur, (uint32_t*)J->keys2.p);
+    hipLaunchKernelGGL(k_keys_partition, per_class, dim3(256), P.n_sub * 12, ks,
+                       (const uint32_t*)sk.keys, (const unsigned long long*)sk.fill, sk.cap, sh, P.n_sub, cur, (uint32_t*)J->keys2.p);
     HIP_TRY(hipGetLastError());
     if (two) HIP_TRY(hipEventRecord(J->ev_part[sl], ks));
     ++J->n_pieces; J->count_due = true;
@@ -452,59 +432,38 @@ int scan_keys_piece(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, ui
     return 0;
 }
 
-// the pieces of reads [r0, r1): of piece_reads, and -- where the range ends the reads and the keys are counted under the
-// next scan -- halving over the last ones down to tail_reads, so that little is left to count when the last scan ends
-// (a piece's counting takes under half its scan's time)
-inline std::vector<uint64_t> scan_piece_sizes(const ScanJob* J, uint64_t n, bool last)
-{
-    std::vector<uint64_t> tail;
-    uint64_t t_sum = 0;
-    if (last && J->n_slices > 1 && J->tail_reads)
-        for (uint64_t t = J->tail_reads; t < J->piece_reads && t_sum + t < n; t *= 2) { tail.push_back(t); t_sum += t; }
-    std::vector<uint64_t> v;
-    const uint64_t body = n - t_sum, nb = (body + J->piece_reads - 1) / J->piece_reads;
-    for (uint64_t i = 0, at = 0; i < nb; ++i) { const uint64_t e = body * (i + 1) / nb; v.push_back(e - at); at = e; }
-    v.insert(v.end(), tail.rbegin(), tail.rend());
-    return v;
-}
-
 template <int K>
 int scan_range(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, uint64_t r0, uint64_t r1)
 {
     if (r1 <= r0) return 0;
     const PartParams& pp = J->pp;
-    const bool by_class = J->by_class;
-    unsigned grid = (unsigned)((r1 - r0 + PART_THREADS - 1) / PART_THREADS);
-    static const unsigned scan_blocks = getenv("DFK_SCAN_BLOCKS") ? (unsigned)atoi(getenv("DFK_SCAN_BLOCKS")) : 0;
-    if (by_class) grid = std::min<unsigned>(grid, (scan_blocks ? scan_blocks : 128u) * (unsigned)c->prop.multiProcessorCount);   // grid-stride: class counts are flushed once per block (12 blocks per CU: 57 ms per 225 M reads, 128: 47 ms)
-    else if (scan_blocks) grid = std::min<unsigned>(grid, scan_blocks * (unsigned)c->prop.multiProcessorCount);
-    const size_t lds_a = (sizeof(uint32_t) + 1) * pp.W * PART_THREADS + sizeof(uint32_t) * PART_RING * PART_THREADS + (by_class ? J->n_bins * 4 : 0);
+    const ScanPlan& P = J->plan;
+    const unsigned grid = scan_grid(P, r1 - r0, (unsigned)c->prop.multiProcessorCount);
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
     J->ev.emplace_back(e0, e1);
     HIP_TRY(hipEventRecord(e0, c->stream));
     // the minimizer length everybody uses gets the scan whose window lives in registers (all three K since the positions are
     // packed four to a register); other lengths the general one
-    if (J->keyed) {
+    if (P.keyed) {
         uint64_t p0 = r0;
-        for (uint64_t m : scan_piece_sizes(J, r1 - r0, r1 == in.n_reads)) {
+        for (uint64_t m : scan_piece_sizes(P, r1 - r0, r1 == in.n_reads)) {
             int rc = scan_keys_piece<K>(c, in, T, J, p0, p0 + m); if (rc) return rc;
             p0 += m;
         }
         // (ms_part_count runs until the bucket totals exist)
         if (r1 == in.n_reads && J->count_due) { int rc = scan_keys_count(c, T, J); if (rc) return rc; }
-    } else if (scan_takes_ranges<K>(c)) {
-        const size_t lds_r = SCAN_RUN_LDS + (by_class ? J->n_bins * 4 : 0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, false>), dim3(grid), dim3(PART_THREADS), lds_r, c->stream,
+    } else if (P.register_scan) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, false>), dim3(grid), dim3(PART_THREADS), scan_lds(P), c->stream,
                            in.packed, in.packed_bytes, in.base_off, (const uint32_t*)c->good_len.p, r0, r1, pp,
-                           (unsigned long long*)T->acc.p, (unsigned long long*)T->class_hist.p, (unsigned long long*)J->d_n.p, J->ovf_cap,
+                           (unsigned long long*)T->acc.p, (unsigned long long*)T->class_hist.p, (unsigned long long*)J->d_n.p, P.ovf_cap,
                            (uint32_t*)J->ovf_tmp.p, (uint4*)T->summ.p, (uint32_t*)T->classes.p, ScanKeys{});
     } else {
         if (r0 != 0 || r1 != in.n_reads) return fail(DFK_E_STATE, "the general scan takes every read at once");
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_partition<K, false>), dim3(grid), dim3(PART_THREADS), lds_a, c->stream,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_partition<K, false>), dim3(grid), dim3(PART_THREADS), scan_lds(P), c->stream,
                            in.packed, in.packed_bytes, in.base_off, (const uint32_t*)c->good_len.p, in.bc,
                            (int64_t)c->cfg.ign_bc_below, in.n_reads, pp, (unsigned long long*)T->acc.p, (unsigned long long*)T->class_hist.p,
-                           (unsigned long long*)J->d_n.p, J->ovf_cap, (uint4*)J->ovf_tmp.p, (uint4*)T->summ.p,
+                           (unsigned long long*)J->d_n.p, P.ovf_cap, (uint4*)J->ovf_tmp.p, (uint4*)T->summ.p,
                            (const uint32_t*)nullptr, (uint64_t)0, (const uint64_t*)nullptr, (uint32_t*)T->classes.p);
     }
     HIP_TRY(hipGetLastError());
@@ -522,7 +481,7 @@ int scan_end(dfk_ctx* c, const Inputs& in, uint64_t n_inst, BucketTable* T, Scan
     if (in.n_reads) {
         HIP_TRY(hipMemcpyAsync(&T->n_ovf, J->d_n.p, 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (T->n_ovf > J->ovf_cap) {                                    // long reads: most summaries overflow
+        if (T->n_ovf > J->plan.ovf_cap) {                                    // long reads: most summaries overflow
             c->release(J->ovf_tmp);
             rc = c->alloc(J->ovf_tmp, in.n_reads * 4, "overflow read list (scratch)"); if (rc) return rc;
             HIP_TRY(hipMemsetAsync(J->d_n.p, 0, 16, c->stream));
@@ -544,19 +503,20 @@ int scan_end(dfk_ctx* c, const Inputs& in, uint64_t n_inst, BucketTable* T, Scan
     for (auto& e : J->ev) { float m = 0; if (hipEventElapsedTime(&m, e.first, e.second) == hipSuccess) ms += m; }
     c->st.ms_part_count = ms; c->st.reserved[6] = J->ev.size();          // (launches of the counting scan: 1, or the pieces of run_under_upload)
     TRACE("%llu of %llu reads have more than %d runs", (unsigned long long)T->n_ovf, (unsigned long long)in.n_reads, SUMMARY_RUNS);
-    if (J->by_class) {
-        T->h_class.assign(J->n_bins, 0);
-        HIP_TRY(hipMemcpyAsync(T->h_class.data(), T->class_hist.p, J->n_bins * 8, hipMemcpyDeviceToHost, c->stream));
+    const uint64_t nb = J->plan.nb, n_bins = J->plan.n_bins;
+    if (J->plan.by_class) {
+        T->h_class.assign(n_bins, 0);
+        HIP_TRY(hipMemcpyAsync(T->h_class.data(), T->class_hist.p, n_bins * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         T->n_records = T->n_inst = 0;
-        for (uint64_t i = 0; i < J->n_bins / 2; ++i) { T->n_records += T->h_class[i]; T->n_inst += T->h_class[J->n_bins / 2 + i]; }
-    } else { rc = table_totals(c, T->acc, J->nb, &T->n_records, &T->n_inst); if (rc) return rc; }
-    TRACE("partition count pass done (%llu buckets, %llu records%s)", (unsigned long long)J->nb, (unsigned long long)T->n_records, J->ev.size() > 1 ? ", in ranges under the upload" : "");
+        for (uint64_t i = 0; i < n_bins / 2; ++i) { T->n_records += T->h_class[i]; T->n_inst += T->h_class[n_bins / 2 + i]; }
+    } else { rc = table_totals(c, T->acc, nb, &T->n_records, &T->n_inst); if (rc) return rc; }
+    TRACE("partition count pass done (%llu buckets, %llu records%s)", (unsigned long long)nb, (unsigned long long)T->n_records, J->ev.size() > 1 ? ", in ranges under the upload" : "");
     if (T->n_inst != n_inst)
         return fail(DFK_E_HIP, "partition count pass saw %llu instances, trim saw %llu%s",
                     (unsigned long long)T->n_inst, (unsigned long long)n_inst,
                     (n_inst - T->n_inst) % (1ull << 32) == 0 ? " (a fine bucket with 2^32 or more instances: its counter keeps 32 bits)" : "");
-    c->st.n_records = T->n_records; c->st.n_buckets = J->nb;
+    c->st.n_records = T->n_records; c->st.n_buckets = nb;
     return 0;
 }
 
@@ -1313,15 +1273,8 @@ int stage_adjacency(dfk_ctx* c)
 
 uint32_t pick_log2_nb(uint64_t n_inst, uint32_t log2_world)
 {
-    // fine buckets of ~430-850 instances (the count is a power of two); an item packs several of them up to its
-    // instance budget.  Measured on configs[1] at K = 40/48/60: 2^27 buckets beat 2^28 (the scan's atomics run on a
-    // 1 GB counter table instead of 2 GB: -7..-23 ms) and 2^26 (items overflow their tables: +190 ms).
-    // (When sharded, the record header keeps 24 bits of the bucket id inside the pass for the receiver's
-    // regroup: dfk_shard_plan asks for enough passes that a pass has <= 2^24 buckets per owner.)
     static const uint64_t per = getenv("DFK_INST_PER_BUCKET") ? (uint64_t)atoll(getenv("DFK_INST_PER_BUCKET")) : 850;
-    uint32_t l = ceil_log2(n_inst / per + 1);
-    l = std::max<uint32_t>(l, 4 + log2_world);
-    return std::min<uint32_t>(l, 28);
+    return dfk::pick_log2_nb(n_inst, log2_world, per);
 }
 
 // the numbers plan_range (dfk_arena.h) works from
@@ -1500,9 +1453,9 @@ int run_under_upload(dfk_ctx* c, const Inputs& in, const uint8_t* h_packed)
 {
     const uint64_t n = in.n_reads, pb = in.packed_bytes;
     const uint64_t seg_env = getenv("DFK_UPLOAD_SEGMENT") ? (uint64_t)atoll(getenv("DFK_UPLOAD_SEGMENT")) : 0;      // (tests: small pieces)
-    const uint64_t seg = seg_env ? std::max<uint64_t>(64, seg_env & ~63ull) : std::max<uint64_t>(256ull << 20, ((pb / 12) + (64ull << 20)) & ~((64ull << 20) - 1));
+    const uint64_t seg = upload_segment_bytes(pb, seg_env);
     // where the reads end, coarsely
-    const uint64_t stride = std::max<uint64_t>(1, (n + 32767) / 32768), n_samp = n / stride + 2;
+    const uint64_t stride = offset_sampling(n).stride, n_samp = offset_sampling(n).n_samp;
     std::vector<uint64_t> samp(n_samp);
     {
         DevBuf d; int rc = c->alloc(d, n_samp * 8, "offset samples", Place::Low); if (rc) return rc;
@@ -1512,10 +1465,6 @@ int run_under_upload(dfk_ctx* c, const Inputs& in, const uint8_t* h_packed)
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->release(d);
     }
-    auto reads_within = [&](uint64_t bytes) -> uint64_t {              // reads whose bases end at or before `bytes` (a multiple of the stride, or all)
-        const uint64_t i = (uint64_t)(std::upper_bound(samp.begin(), samp.end(), bytes) - samp.begin());   // samp[i-1] <= bytes < samp[i]
-        return i ? std::min<uint64_t>((i - 1) * stride, n) : 0;
-    };
     Prescan pre;
     // ---- the trim beside the first piece
     int trim_rc = 0; std::string trim_err;
@@ -1541,7 +1490,7 @@ int run_under_upload(dfk_ctx* c, const Inputs& in, const uint8_t* h_packed)
     rc = scan_begin<K>(c, in, 0, 0, &pre.T, false, &J); if (rc) return rc;
     uint64_t scanned = 0;
     for (;;) {
-        const uint64_t r1 = sent >= pb ? n : reads_within(sent);
+        const uint64_t r1 = sent >= pb ? n : reads_within(samp, stride, n, sent);
         rc = scan_range<K>(c, in, &pre.T, &J, scanned, r1); if (rc) return rc;
         scanned = std::max(scanned, r1);
         if (sent >= pb) break;

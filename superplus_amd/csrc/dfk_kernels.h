@@ -5,6 +5,7 @@
 #include <type_traits>
 #include "dfk_device.h"
 #include "dfk_fallback.h"   // ItemRange, WgOut, HotItem, BigItem, COUNT_CHUNK: what the kernels share with the host's fallback planner
+#include "dfk_scan_plan.h"  // PART_THREADS, PART_RING, PART_CLASSES, SUMMARY_RUNS, ScanKeys, SCAN_STAGE, KEY_SUB_BITS, SCAN_*_LDS: ... with the counting scan's plan
 
 namespace dfk {
 
@@ -136,14 +137,7 @@ __host__ __device__ inline uint32_t sweep_class_mask(uint32_t sub_lo, uint32_t s
     return upto_b & ~((1u << a) - 1u);
 }
 
-constexpr int PART_THREADS = 128;
-constexpr int PART_RING = 2;          // words of its read a lane of the general counting scan (k_partition) keeps staged in LDS
-// Per-read run summary written by the counting scan (16 bytes): bits 0-3 = number of runs (super-k-mers) or
-// SUMMARY_OVERFLOW, then from bit 8 twelve bits per run: nk (6) | offset of its minimizer from the run's
-// first k-mer (6, < W).  The scatter passes rebuild each run's bucket from the 2M bits at that offset
-// instead of scanning the read again.
-constexpr int SUMMARY_RUNS = 10;
-constexpr uint32_t SUMMARY_OVERFLOW = 15;
+constexpr uint32_t SUMMARY_OVERFLOW = 15;   // a run summary's count field (dfk_scan_plan.h) when the read has more than SUMMARY_RUNS runs
 
 // pass-local number of a global fine bucket id, or ~0 if the bucket is not in this pass
 __device__ __forceinline__ uint32_t pass_local(uint32_t bucket, const PartParams& pp)
@@ -195,10 +189,7 @@ __device__ __forceinline__ void emit_record(const uint32_t* __restrict__ words, 
     records[2 * dst_index + 1] = b;
 }
 
-// Sharded runs do not need per-bucket counts on the sending side (the owner regroups what it receives), only
-// how many records go to each owner in each pass: bucket space of an owner cut into PART_CLASSES equal
-// classes; a pass is a whole number of classes.
-constexpr uint32_t PART_CLASSES = 64;
+// the class (dfk_scan_plan.h: PART_CLASSES) a sharded run counts a bucket's records under
 __device__ __forceinline__ uint32_t class_bin(uint32_t bucket, const PartParams& pp)
 {
     const uint32_t ls = pp.log2_nb - pp.log2_world;
@@ -450,14 +441,7 @@ __device__ __forceinline__ void static_for(F&& f)
 // (k_keys_subcount), their offsets (k_keys_offsets), a partition of every class slice into sub-slices of 2^KEY_SUB_BITS
 // buckets (k_keys_partition), and per sub-slice an LDS table ADDED into bucket_acc (k_keys_count).  Keys that find their
 // class slice full are counted with the old global atomic on the spot, so the result never depends on the room given.
-struct ScanKeys {
-    uint32_t* keys;                   // [n_cls][cap] keys of each class
-    unsigned long long* fill;         // [n_cls] keys reserved in each class slice (may pass cap: the rest were counted directly)
-    uint64_t cap;                     // room of a class slice
-    uint32_t ib;                      // bits of a bucket within its class: log2_nb - min(6, log2_nb)
-};
-constexpr int SCAN_STAGE = 1536;      // keys a scan block stages (5 B each): with the scan's own 7.5 KB, under 16 KB -- ten blocks a CU at K=40
-constexpr uint32_t KEY_SUB_BITS = 14; // buckets of a sub-slice: 2^14 u64 counters = 128 KB of LDS
+// (ScanKeys, SCAN_STAGE, KEY_SUB_BITS and the scan's LDS sizes: dfk_scan_plan.h)
 constexpr uint32_t KEY_TILE = 4096;   // keys a partition block holds in registers and reserves room for at once (one atomic per sub-slice present)
 
 template <int K, int M, bool KEYS>
@@ -676,10 +660,6 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
         for (uint32_t i = threadIdx.x; i < n_bins; i += PART_THREADS) if (lh[i]) atomicAdd(&class_hist[i], (unsigned long long)lh[i]);
     }
 }
-// LDS of the scan: its runs (bucket and summary field of each), then the class counts or (KEYS) the staging
-constexpr size_t SCAN_RUN_LDS = (sizeof(uint32_t) + sizeof(uint16_t)) * SUMMARY_RUNS * PART_THREADS;
-constexpr size_t SCAN_STAGE_LDS = (sizeof(uint32_t) + 1) * SCAN_STAGE + (sizeof(unsigned long long) + sizeof(uint32_t)) * PART_CLASSES + sizeof(uint32_t);
-static_assert(SCAN_RUN_LDS + SCAN_STAGE_LDS <= 16384, "ten scan blocks a CU (160 KB of LDS)");
 
 // The three kernels below run on the second stream beside the NEXT piece's scan, in what its waves leave of a SIMD (64 VGPRs
 // at K=48, 32 at K=40), so a wave is at most 32 VGPRs and keeps KEY_VECS 16-byte loads in flight.  A thread's j-th vector

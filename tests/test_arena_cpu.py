@@ -1,8 +1,11 @@
 """The device arena and the pass planner (superplus_amd/csrc/dfk_arena.h) are host code that never touches device
 memory: they run here, on a CPU, against a backing store that only counts.  So do the decisions of the count stage's
-hot-bucket fallback (superplus_amd/csrc/dfk_fallback.h): plain arithmetic over instance counts."""
+hot-bucket fallback (superplus_amd/csrc/dfk_fallback.h): plain arithmetic over instance counts.  And so does the plan of
+the counting scan (superplus_amd/csrc/dfk_scan_plan.h): plain arithmetic over read and byte counts."""
 import os
 import subprocess
+
+import pytest
 
 
 def test_cpp_arena_and_planner(tmp_path):
@@ -27,3 +30,18 @@ def test_cpp_fallback_planner(tmp_path):
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-o", exe, os.path.join(root, "tests", "cpp", "test_fallback.cc")])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "FAILED" not in out.stdout and out.stdout.count(": ok") == 10, out.stdout + out.stderr
+
+
+@pytest.mark.parametrize("flags", [["-O1"], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]], ids=["plain", "sanitized"])
+def test_cpp_scan_plan(tmp_path, flags):
+    """tests/cpp/test_scan_plan.cc: whether the counting scan builds run keys, their classes and sub-slices, the room of a
+    class slice and the scratch sizes, the pieces of a range with their halving tail, grids, LDS bytes, the number of fine
+    buckets, the upload's pieces and the reads a piece completes -- against tables recorded from the code before it moved
+    into the header (tests/cpp/scan_plan_expected.h: K = 40, 48, 60, bucket counts on both sides of every threshold, 1 to
+    1.8x10^9 reads, every switch; the default benchmark's nine pieces among them), the properties of each over 10^4 seeded
+    random cases, and the per-piece step replayed over two key slices.  A stand-alone program, also under the sanitizers."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "test_scan_plan")
+    subprocess.check_call(["g++", *flags, "-std=c++17", "-Wall", "-o", exe, os.path.join(root, "tests", "cpp", "test_scan_plan.cc")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "FAILED" not in out.stdout and out.stdout.count(": ok") == 8, out.stdout + out.stderr

@@ -73,6 +73,30 @@ def test_many_pieces_on_two_slices(oracle, golden_dir, monkeypatch, K, which):
         _same(got, whole, f"{which} K={K} {way}")
 
 
+@pytest.mark.parametrize("K", [40, 48])
+def test_halving_tail_of_the_last_range(oracle, monkeypatch, K):
+    """(a') The pieces of the range that ends the reads halve down to DFK_SCAN_KEY_TAIL: pieces of at most 4096 reads with a
+    tail of 256, so the last range ends in pieces of 2048, 1024, 512 and 256 reads -- from device inputs, from host arrays,
+    and under the upload, where only the final range has the tail.  Each way gives the one-piece run's result and the
+    oracle's; so does DFK_SCAN_KEY_TAIL=0 (equal pieces)."""
+    rs, min_freq = util.make_set(91, 60000, 6000), 3
+    ref = oracle.run(rs["packed"], rs["base_off"], rs["read_len"], rs["pq_bytes"], rs["pq_off"], rs["bc"], K=K, min_freq=min_freq)
+    whole, d = _run(rs, K, min_freq=min_freq)
+    util.check_parity(ref, d)
+    d.close()
+    for tail in ("256", "0"):
+        for way, how in _WAYS.items():
+            with monkeypatch.context() as mp:
+                for k, v in how["env"].items():
+                    mp.setenv(k, v)
+                mp.setenv("DFK_SCAN_KEY_PIECE", "4096")
+                mp.setenv("DFK_SCAN_KEY_TAIL", tail)
+                got, d = _run(rs, K, device_inputs=how["device_inputs"], min_freq=min_freq)
+                util.check_parity(ref, d)
+                d.close()
+            _same(got, whole, f"synthetic K={K} tail {tail} {way}")
+
+
 def _poly_a_set(n_poly, seed=23):
     """The reads of test_one_bucket_beyond_its_class_slice: n_poly poly-A reads (two runs each, all of one fine bucket), then
     3000 random reads of which each occurs three times."""
