@@ -8,6 +8,7 @@
 // Kernels: dfk_paths_kernels.h.  Host side here: the HyperBasevector's tables as flat device arrays, the batch loop (the
 // scratch of a batch -- parts, path room, decoded qualities -- is sized by the reads' k-mer counts), the file.
 #include "dfk_check_kernels.h"
+#include "dfk_paths_plan.h"   // the host decisions of everything here and in dfk_paths_shard.inc: batches, file layouts, ranges, passes, grids
 
 namespace {
 
@@ -112,6 +113,18 @@ PathGraph path_graph_of(HostGraph* G, PathState* P)
                      (uint32_t)G->ce.size(), (uint32_t)G->he.size(), (uint32_t)G->n_vertices, (uint64_t)(G->d_store.bytes / 4)};
 }
 
+// the switches of dfk_paths_plan.h, as the environment sets them now
+PathSwitches path_switches()
+{
+    PathSwitches sw;
+    if (const char* e = getenv("DFK_PATH_SLOTS")) sw.slots = (uint32_t)std::max(1, atoi(e));
+    sw.no_filter = getenv("DFK_NO_FILTER") != nullptr;
+    if (const char* e = getenv("DFK_PATH_BATCH_READS")) sw.batch_reads = std::max<uint64_t>(1, (uint64_t)atoll(e));
+    if (const char* e = getenv("DFK_PIDX_RANGE_PAIRS")) sw.pidx_range_pairs = std::max<uint64_t>(1, (uint64_t)atoll(e));
+    if (const char* e = getenv("DFK_DUP_PASSES")) sw.dup_passes = (uint32_t)std::min<long long>(1024, std::max<long long>(1, atoll(e)));
+    return sw;
+}
+
 template <int K>
 int paths_build_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in)
 {
@@ -136,7 +149,7 @@ int paths_build_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in)
     // 64-bit scan (slots low, quality bytes high), neither of which may pass 2^32.
     uint32_t max_len = 0;
     if (n) {
-        const unsigned g = (unsigned)std::min<uint64_t>((n + 255) / 256, 32ull * cus);
+        const unsigned g = grid_256(n, cus);
         hipLaunchKernelGGL(k_check_tables, dim3(g), dim3(256), 0, c->stream, in.base_off, in.packed_bytes, in.read_len, in.pq_off, in.pq_bytes, n, (unsigned int*)ctr.p);
         hipLaunchKernelGGL(k_max_u32, dim3(g), dim3(256), 0, c->stream, in.read_len, n, (unsigned int*)ctr.p + 1);
         HIP_TRY(hipGetLastError());
@@ -148,15 +161,10 @@ int paths_build_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in)
         if (max_len > 65535u) return fail(DFK_E_ARG, "paths: a read of %u bases (at most 65535)", max_len);
         HIP_TRY(hipMemsetAsync(ctr.p, 0, 32, c->stream));
     }
-    const uint64_t q_per_read = ((uint64_t)max_len + 3) & ~3ull, s_per_read = max_len >= (uint32_t)K ? max_len - K + 1 : 1;
-    const uint64_t nb_bound = std::max<uint64_t>(1, std::min<uint64_t>(0xFFFFFFFFull / std::max<uint64_t>(1, q_per_read), 0xFFFFFFFFull / s_per_read) - 1);
-    // Per read of s slots (k-mer positions) a batch holds 16 s bytes of parts, 8 s + 8 of path room, s + K of
-    // qualities, 24 of bookkeeping and 12 of results; the output (8 + 4 per path edge, + 8 of offset) stays.  A batch takes
-    // what a third of the free room pays for, at a guess of K + 6 slots per read -- checked against the real slot count.
     // what MarkDups (row f-4) will want of every read, while the reads are here
     rc = c->alloc(P->digest, std::max<uint64_t>(1, n) * 4, "read digests"); if (rc) return rc;
     if (n) {
-        hipLaunchKernelGGL(k_read_digest, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream, in.packed, in.base_off, in.read_len,
+        hipLaunchKernelGGL(k_read_digest, dim3(grid_256(n, cus)), dim3(256), 0, c->stream, in.packed, in.base_off, in.read_len,
                            in.pq, in.pq_off, in.pq_bytes, n, (uint32_t*)P->digest.p);
         HIP_TRY(hipGetLastError());
     }
@@ -169,106 +177,94 @@ int paths_build_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in)
     // the filter in front of the index (dfk_paths_kernels.h): two bytes per k-mer, if the device has them to spare
     DevBuf filter;
     KmerFilter kf{nullptr, 0};
+    const PathSwitches sw = path_switches();
     {
-        const uint64_t n_kmers = pt.start[pt.n_parts], words = std::max<uint64_t>(64, n_kmers / 2), free_now = c->largest_allocatable();
-        if (G->d_filter.p && G->filter_words == words && !getenv("DFK_NO_FILTER")) {         // made under the graph's numbering (dfk_graph.inc)
+        const uint64_t n_kmers = pt.start[pt.n_parts], free_now = c->largest_allocatable();
+        const PathFilterPlan fp = plan_path_filter(n_kmers, n, free_now, G->d_filter.p ? G->filter_words : 0, sw.no_filter);
+        if (fp.use == PathFilter::Reuse) {                                     // made under the graph's numbering (dfk_graph.inc)
             filter = G->d_filter; G->d_filter = DevBuf{}; G->filter_words = 0;
-            kf = KmerFilter{(const uint32_t*)filter.p, words};
-        } else if (!getenv("DFK_NO_FILTER") && n_kmers && free_now > words * 4 + n * 18 + (4ull << 30)) {
-            rc = c->alloc(filter, words * 4, "k-mer filter"); if (rc) return rc;
-            HIP_TRY(hipMemsetAsync(filter.p, 0, words * 4, c->stream));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_filter_build<K>), dim3((unsigned)std::min<uint64_t>((n_kmers + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream,
-                               pt, n_kmers, (uint32_t*)filter.p, words);
+        } else if (fp.use == PathFilter::Build) {
+            rc = c->alloc(filter, fp.words * 4, "k-mer filter"); if (rc) return rc;
+            HIP_TRY(hipMemsetAsync(filter.p, 0, fp.words * 4, c->stream));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_filter_build<K>), dim3(grid_256(n_kmers, cus)), dim3(256), 0, c->stream,
+                               pt, n_kmers, (uint32_t*)filter.p, fp.words);
             HIP_TRY(hipGetLastError());
-            kf = KmerFilter{(const uint32_t*)filter.p, words};
         } else TRACE("paths: no room for the k-mer filter (%.1f GB free)", free_now / 1e9);
+        if (filter.p) kf = KmerFilter{(const uint32_t*)filter.p, fp.words};
     }
-    // A batch's scratch comes out of what is free NOW minus what the batches still to come will leave behind (their share of
-    // the file: ~13 bytes of data and 4 of offset per read), so that the last batches are not squeezed into nothing.
-    // Per read: 16 bytes a part and 8 a path slot, its bases in decoded qualities, 28 of bookkeeping.  PATH_SLOTS slots do for
-    // nearly every read (five wrong bases make eleven parts) where one per k-mer position would be 53 to 103: a batch in which
-    // a read wants more says so and is done again with all of them.
-    const uint32_t PATH_SLOTS = getenv("DFK_PATH_SLOTS") ? (uint32_t)std::max(1, atoi(getenv("DFK_PATH_SLOTS"))) : 12u;
-    uint64_t r0 = 0, file_at = 24, placed = 0, path_edges = 0;
+    // the batches: PathBatcher (dfk_paths_plan.h) says which reads, with how many slots, in what room and where in the file
+    PathBatcher bp(n, path_batch_bound(max_len, (uint32_t)K), sw);
+    uint64_t placed = 0, path_edges = 0;
     unsigned bad = 0;
-    bool all_slots = false;                                                    // this batch: one slot per k-mer position
-    while (r0 < n) {
-        const uint32_t cap = all_slots ? 0xFFFFFFFFu : PATH_SLOTS;
-        const uint64_t free_now = c->largest_allocatable(), to_come = (n - r0) * 18;
-        const uint64_t room = free_now > to_come + (256ull << 20) ? free_now - to_come : free_now / 8;
-        const uint64_t per_read_guess = 24ull * std::min<uint32_t>(cap, 64) + 8 + 104 + 64;
-        uint64_t nb = std::min<uint64_t>(n - r0, std::max<uint64_t>(1, room / 2 / per_read_guess));
-        nb = std::min<uint64_t>(nb, nb_bound);                                 // (k_path_slots: both offsets of a read in one word, 32 bits each)
+    while (bp.more()) {
+        bp.begin(c->largest_allocatable());
+        const uint64_t r0 = bp.r0;
         DevBuf slots, slot_off;
-        bool again = false;
+        uint64_t total = 0, qtotal = 0;
         for (;;) {                                                              // shrink until the real scratch fits
-            rc = c->alloc(slots, (nb + 1) * 8, "path slots", Place::Low); if (rc) return rc;
-            rc = c->alloc(slot_off, (nb + 1) * 8, "path slot offsets", Place::Low); if (rc) return rc;
-            const unsigned grid = (unsigned)std::min<uint64_t>((nb + 255) / 256, 16ull * cus);
-            hipLaunchKernelGGL(k_path_slots, dim3(grid), dim3(256), 0, c->stream, in.read_len, r0, nb, (uint32_t)K, cap, (uint64_t*)slots.p);
-            HIP_TRY(hipMemsetAsync((uint64_t*)slots.p + nb, 0, 8, c->stream));
-            rc = device_scan(c, (const uint64_t*)slots.p, (uint64_t*)slot_off.p, nb + 1); if (rc) return rc;
+            rc = c->alloc(slots, (bp.nb + 1) * 8, "path slots", Place::Low); if (rc) return rc;
+            rc = c->alloc(slot_off, (bp.nb + 1) * 8, "path slot offsets", Place::Low); if (rc) return rc;
+            hipLaunchKernelGGL(k_path_slots, dim3(grid_256(bp.nb, cus, 16)), dim3(256), 0, c->stream, in.read_len, r0, bp.nb, (uint32_t)K, bp.cap, (uint64_t*)slots.p);
+            HIP_TRY(hipMemsetAsync((uint64_t*)slots.p + bp.nb, 0, 8, c->stream));
+            rc = device_scan(c, (const uint64_t*)slots.p, (uint64_t*)slot_off.p, bp.nb + 1); if (rc) return rc;
             uint64_t both = 0;
-            HIP_TRY(hipMemcpyAsync(&both, (uint64_t*)slot_off.p + nb, 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(&both, (uint64_t*)slot_off.p + bp.nb, 8, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
-            const uint64_t total = both & 0xFFFFFFFFull, qtotal = both >> 32;
-            const uint64_t need = 24 * total + qtotal + nb * (8 + 12 + 16) + 4096;
-            if (need <= room || nb == 1) {
-                c->release(slots);
-                DevBuf parts, path, quals, o_off, o_len, o_first, sizes, size_off;
-                PathBatch B; B.r0 = r0; B.n = nb; B.file_base = file_at;
-                if ((rc = c->alloc(parts, std::max<uint64_t>(1, total) * sizeof(PartD), "path parts", Place::Low)) ||
-                    (rc = c->alloc(path, (2 * total + 2 * nb) * 4, "path room", Place::Low)) ||
-                    (rc = c->alloc(quals, qtotal + 64, "decoded qualities", Place::Low)) ||
-                    (rc = c->alloc(o_off, nb * 4, "path offsets", Place::Low)) || (rc = c->alloc(o_len, nb * 4, "path lengths", Place::Low)) ||
-                    (rc = c->alloc(o_first, nb * 4, "path starts", Place::Low)) ||
-                    (rc = c->alloc(sizes, (nb + 1) * 8, "element sizes", Place::Low)) || (rc = c->alloc(size_off, (nb + 1) * 8, "element offsets", Place::Low)))
-                    return rc;
-                HIP_TRY(hipMemsetAsync(ctr.p, 0, 32, c->stream));                // this batch's: reads placed, path edges, flags
-                const unsigned pgrid = (unsigned)std::min<uint64_t>((nb + 255) / 256, 64ull * cus);
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_reads<K>), dim3(pgrid), dim3(256), 0, c->stream, pt, (const uint32_t*)G->d_index.p, G->index_slots, kf, pg,
-                                   in.packed, in.packed_bytes, in.base_off, in.read_len, in.pq, in.pq_off, r0, nb, (const uint64_t*)slot_off.p,
-                                   (PartD*)parts.p, (int32_t*)path.p, (uint8_t*)quals.p, (int32_t*)o_off.p, (uint32_t*)o_len.p, (uint32_t*)o_first.p,
-                                   (unsigned long long*)ctr.p, (unsigned int*)((char*)ctr.p + 16));
-                hipLaunchKernelGGL(k_path_sizes, dim3(grid), dim3(256), 0, c->stream, (const uint32_t*)o_len.p, nb, (uint64_t*)sizes.p);
-                HIP_TRY(hipMemsetAsync((uint64_t*)sizes.p + nb, 0, 8, c->stream));
-                HIP_TRY(hipGetLastError());
-                rc = device_scan(c, (const uint64_t*)sizes.p, (uint64_t*)size_off.p, nb + 1); if (rc) return rc;
-                uint64_t h[4] = {};
-                HIP_TRY(hipMemcpyAsync(&B.var_bytes, (uint64_t*)size_off.p + nb, 8, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(hipMemcpyAsync(h, ctr.p, 32, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                again = ((unsigned)h[2] & 32u) != 0;
-                if (!again) {
-                    bad |= (unsigned)h[2]; placed += h[0]; path_edges += h[1];
-                    if (B.var_bytes >= (1ull << 32)) return fail(DFK_E_ARG, "a batch of %llu reads holds %llu bytes of paths: its offsets keep 32 bits", (unsigned long long)nb, (unsigned long long)B.var_bytes);
-                    if ((rc = c->alloc(B.var, std::max<uint64_t>(4, B.var_bytes), "a.paths data")) || (rc = c->alloc(B.elem_off, nb * 4, "a.paths offsets"))) return rc;
-                    hipLaunchKernelGGL(k_path_emit, dim3(grid), dim3(256), 0, c->stream, (const uint64_t*)size_off.p, (const uint64_t*)slot_off.p, (const int32_t*)path.p,
-                                       (const int32_t*)o_off.p, (const uint32_t*)o_len.p, (const uint32_t*)o_first.p, nb, (uint32_t*)B.var.p, (uint32_t*)B.elem_off.p);
-                    unsigned bflag = 0;
-                    if (mark_bads) {                                          // on the paths that stay: this attempt's, as k_path_emit left them
-                        bads_timer->start();
-                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bad_sums<K>), dim3(pgrid), dim3(256), 0, c->stream, pg, in.packed, in.packed_bytes, in.base_off, in.read_len,
-                                           in.pq, in.pq_off, (const uint32_t*)B.var.p, (const uint32_t*)B.elem_off.p, nb, r0, B.var_bytes,
-                                           (uint16_t*)P->bad_sums.p, (unsigned int*)((char*)ctr.p + 24));
-                        bads_ms += bads_timer->stop();
-                        HIP_TRY(hipMemcpyAsync(&bflag, (char*)ctr.p + 24, 4, hipMemcpyDeviceToHost, c->stream));
-                    }
-                    HIP_TRY(hipGetLastError());
-                    HIP_TRY(hipStreamSynchronize(c->stream));
-                    bad |= bflag;
-                }
-                c->release(parts); c->release(path); c->release(quals); c->release(o_off); c->release(o_len); c->release(o_first);
-                c->release(sizes); c->release(size_off); c->release(slot_off);
-                if (!again) { file_at += B.var_bytes; P->batches.push_back(B); sink_push(P, B); }
-                break;
-            }
+            total = both & 0xFFFFFFFFull; qtotal = both >> 32;
+            if (bp.fits(total, qtotal)) break;
             c->release(slots); c->release(slot_off);
-            nb = std::max<uint64_t>(1, nb / 2);
         }
-        if (again) { TRACE("paths: a read of [%llu, %llu) wants more than %u slots: the batch again with all", (unsigned long long)r0, (unsigned long long)(r0 + nb), PATH_SLOTS); all_slots = true; continue; }
-        all_slots = false;
-        r0 += nb;
+        c->release(slots);
+        const uint64_t nb = bp.nb;
+        const unsigned grid = grid_256(nb, cus, 16), pgrid = grid_256(nb, cus, 64);
+        const PathScratch sz = bp.scratch(total, qtotal);
+        static_assert(sizeof(PartD) == 16, "PathScratch counts 16 bytes a part");
+        DevBuf parts, path, quals, o_off, o_len, o_first, sizes, size_off;
+        PathBatch B; B.r0 = r0; B.n = nb; B.file_base = bp.file_base;
+        if ((rc = c->alloc(parts, sz.parts, "path parts", Place::Low)) || (rc = c->alloc(path, sz.path, "path room", Place::Low)) ||
+            (rc = c->alloc(quals, sz.quals, "decoded qualities", Place::Low)) ||
+            (rc = c->alloc(o_off, sz.o_off, "path offsets", Place::Low)) || (rc = c->alloc(o_len, sz.o_len, "path lengths", Place::Low)) ||
+            (rc = c->alloc(o_first, sz.o_first, "path starts", Place::Low)) ||
+            (rc = c->alloc(sizes, sz.sizes, "element sizes", Place::Low)) || (rc = c->alloc(size_off, sz.size_off, "element offsets", Place::Low)))
+            return rc;
+        HIP_TRY(hipMemsetAsync(ctr.p, 0, 32, c->stream));                        // this batch's: reads placed, path edges, flags
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_reads<K>), dim3(pgrid), dim3(256), 0, c->stream, pt, (const uint32_t*)G->d_index.p, G->index_slots, kf, pg,
+                           in.packed, in.packed_bytes, in.base_off, in.read_len, in.pq, in.pq_off, r0, nb, (const uint64_t*)slot_off.p,
+                           (PartD*)parts.p, (int32_t*)path.p, (uint8_t*)quals.p, (int32_t*)o_off.p, (uint32_t*)o_len.p, (uint32_t*)o_first.p,
+                           (unsigned long long*)ctr.p, (unsigned int*)((char*)ctr.p + 16));
+        hipLaunchKernelGGL(k_path_sizes, dim3(grid), dim3(256), 0, c->stream, (const uint32_t*)o_len.p, nb, (uint64_t*)sizes.p);
+        HIP_TRY(hipMemsetAsync((uint64_t*)sizes.p + nb, 0, 8, c->stream));
+        HIP_TRY(hipGetLastError());
+        rc = device_scan(c, (const uint64_t*)sizes.p, (uint64_t*)size_off.p, nb + 1); if (rc) return rc;
+        uint64_t h[4] = {};
+        HIP_TRY(hipMemcpyAsync(&B.var_bytes, (uint64_t*)size_off.p + nb, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h, ctr.p, 32, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        const bool again = ((unsigned)h[2] & 32u) != 0;                          // a read wants more slots than it was given
+        if (!again) {
+            bad |= (unsigned)h[2]; placed += h[0]; path_edges += h[1];
+            if (B.var_bytes >= (1ull << 32)) return fail(DFK_E_ARG, "a batch of %llu reads holds %llu bytes of paths: its offsets keep 32 bits", (unsigned long long)nb, (unsigned long long)B.var_bytes);
+            if ((rc = c->alloc(B.var, std::max<uint64_t>(4, B.var_bytes), "a.paths data")) || (rc = c->alloc(B.elem_off, nb * 4, "a.paths offsets"))) return rc;
+            hipLaunchKernelGGL(k_path_emit, dim3(grid), dim3(256), 0, c->stream, (const uint64_t*)size_off.p, (const uint64_t*)slot_off.p, (const int32_t*)path.p,
+                               (const int32_t*)o_off.p, (const uint32_t*)o_len.p, (const uint32_t*)o_first.p, nb, (uint32_t*)B.var.p, (uint32_t*)B.elem_off.p);
+            unsigned bflag = 0;
+            if (mark_bads) {                                                  // on the paths that stay: this attempt's, as k_path_emit left them
+                bads_timer->start();
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bad_sums<K>), dim3(pgrid), dim3(256), 0, c->stream, pg, in.packed, in.packed_bytes, in.base_off, in.read_len,
+                                   in.pq, in.pq_off, (const uint32_t*)B.var.p, (const uint32_t*)B.elem_off.p, nb, r0, B.var_bytes,
+                                   (uint16_t*)P->bad_sums.p, (unsigned int*)((char*)ctr.p + 24));
+                bads_ms += bads_timer->stop();
+                HIP_TRY(hipMemcpyAsync(&bflag, (char*)ctr.p + 24, 4, hipMemcpyDeviceToHost, c->stream));
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            bad |= bflag;
+        }
+        c->release(parts); c->release(path); c->release(quals); c->release(o_off); c->release(o_len); c->release(o_first);
+        c->release(sizes); c->release(size_off); c->release(slot_off);
+        if (!again) { P->batches.push_back(B); sink_push(P, B); }
+        else TRACE("paths: a read of [%llu, %llu) wants more than %u slots: the batch again with all", (unsigned long long)r0, (unsigned long long)(r0 + nb), sw.slots);
+        bp.end(again, B.var_bytes);
     }
     TRACE("paths: %.3f s in, the last batch is launched", wall_now() - t_in);
     c->release(ctr);
@@ -278,14 +274,14 @@ int paths_build_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in)
     if (bad & 4u) return fail(DFK_E_STATE, "paths: a dictionary entry without an edge (the graph does not belong to this dictionary)");
     if (bad & 8u) return fail(DFK_E_HIP, "paths: a path outgrew its read's k-mer count (bound of the scratch layout violated)");
     if (bad & 16u) return fail(DFK_E_INPUT, "paths: a read's PQVec does not hold one quality per base");
-    P->n_reads = n; P->n_placed = placed; P->n_edges = path_edges; P->var_total = file_at - 24; P->built = true;
+    P->n_reads = n; P->n_placed = placed; P->n_edges = path_edges; P->var_total = bp.file_base - 24; P->built = true;
     {   // dfk_paths_digest: the file's elements, whatever batches they were made in
         const unsigned dgrid = 32u * cus;                                       // (a slot pair per block, then the fold: see k_paths_digest)
         DevBuf dg; rc = c->alloc(dg, 32 + 16ull * dgrid, "paths digest", Place::Low); if (rc) return rc;
         HIP_TRY(hipMemsetAsync(dg.p, 0, 32 + 16ull * dgrid, c->stream));
         unsigned long long* slots = (unsigned long long*)dg.p + 4;
         for (const PathBatch& b : P->batches)
-            hipLaunchKernelGGL(k_paths_digest, dim3((unsigned)std::min<uint64_t>((b.n + 255) / 256, dgrid)), dim3(256), 0, c->stream, (const uint32_t*)b.var.p,
+            hipLaunchKernelGGL(k_paths_digest, dim3(grid_256(b.n, cus)), dim3(256), 0, c->stream, (const uint32_t*)b.var.p,
                                (const uint32_t*)b.elem_off.p, b.n, b.r0 + (uint64_t)P->read_id0, b.var_bytes, slots);
         hipLaunchKernelGGL(k_paths_digest_fold, dim3(1), dim3(256), 0, c->stream, (const unsigned long long*)slots, dgrid, (unsigned long long*)dg.p);
         HIP_TRY(hipGetLastError());
@@ -354,10 +350,8 @@ struct FileMap {
     ~FileMap() { drop(); }
 };
 
-// device bytes -> a file, through the transfer lanes (pieces: where from, how many, where to); one writer at a time.
-// A piece with `widen` set is 32-bit values on the device that go to the file as 64-bit ones with `add` added (a feudal
-// file's absolute element offsets, kept per read as 32-bit offsets inside their batch): widened on the host, in the lane.
-struct FilePiece { const char* src; uint64_t bytes, file_off; bool widen = false; uint64_t add = 0; };
+// device bytes -> a file, through the transfer lanes (FilePiece, dfk_paths_plan.h: where from, how many, where to, widened
+// or not); one writer at a time.
 int write_pieces(dfk_ctx* c, int fd, const std::vector<FilePiece>& pieces, const FileMap* fm = nullptr)
 {
     struct Pending { uint64_t bytes = 0, file_off = 0, add = 0; bool widen = false, live = false; };
@@ -427,8 +421,7 @@ void sink_loop(dfk_ctx* c, PathSink* S)
         }
         if (S->rc) continue;                                                   // (a failed file: the rest is only taken off the queue)
         std::vector<FilePiece> pieces;
-        for (const PathBatch& b : take)
-            for (uint64_t o = 0; o < b.var_bytes; o += XFER_CHUNK) pieces.push_back(FilePiece{(const char*)b.var.p + o, std::min<uint64_t>(XFER_CHUNK, b.var_bytes - o), b.file_base + o});
+        for (const PathBatch& b : take) append_pieces(pieces, (const char*)b.var.p, b.var_bytes, b.file_base, XFER_CHUNK);
         if (write_pieces(c, S->fd, pieces)) { S->rc = DFK_E_ARG; S->err = std::string("short write to ") + S->path + " (" + dfk_last_error() + ")"; }
     }
 }
@@ -534,7 +527,8 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
     const uint64_t n_pairs = P->n_edges, n_he = G->he.size();
     if (!n_he) return fail(DFK_E_STATE, "the graph has no edges (the reference asserts the same, PathsIndex.cc:29)");
     const unsigned cus = (unsigned)c->prop.multiProcessorCount;
-    if (tail && (dir.empty() || !n_pairs || n_pairs >= (1ull << 31) || 8 * n_pairs > c->largest_allocatable() / 4 || c->alloc(tail->var, 8 * n_pairs, "a.paths.inv data", Place::Low))) tail = nullptr;
+    const PathSwitches sw = path_switches();
+    if (tail && (!pidx_tail_applies(!dir.empty(), n_pairs, c->largest_allocatable()) || c->alloc(tail->var, 8 * n_pairs, "a.paths.inv data", Place::Low))) tail = nullptr;
     const uint64_t mark = c->alloc_seq;
     int fd = -1;
     uint64_t had = 0;                                                    // bytes a.paths.inv had when it was opened (pages the caller made)
@@ -546,7 +540,7 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
         HIP_TRY(hipMemsetAsync(counts.p, 0, n_he * 4, c->stream));
         uint64_t listed = 0;
         for (const PathBatch& b : P->batches) {
-            hipLaunchKernelGGL(k_pidx_count, dim3((unsigned)std::min<uint64_t>((b.n + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream, (const uint32_t*)b.var.p,
+            hipLaunchKernelGGL(k_pidx_count, dim3(grid_256(b.n, cus)), dim3(256), 0, c->stream, (const uint32_t*)b.var.p,
                                (const uint32_t*)b.elem_off.p, b.n, b.var_bytes, (uint32_t*)counts.p);
             listed += b.var_bytes / 4 - 2 * b.n;
         }
@@ -556,7 +550,7 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
         for (size_t e = 0; e < n_he; ++e) inv[e] = G->he[e].rc ? G->fwd[G->he[e].ce] : G->rev[G->he[e].ce];
         if ((rc = upload_vec(c, d_inv, inv, "involution")) || (rc = c->alloc(c64, (n_he + 1) * 8, "counts", Place::Low)) || (rc = c->alloc(first, (n_he + 1) * 8, "list starts", Place::Low)) ||
             (rc = c->alloc(eo, (n_he + 1) * 8, "list offsets", Place::Low)) || (rc = c->alloc(csb, n_he * 4, "countsb", Place::Low))) return rc;
-        const unsigned egrid = (unsigned)std::min<uint64_t>((n_he + 256) / 256, 32ull * cus);
+        const unsigned egrid = grid_256(n_he + 1, cus);                      // (+ 1: these launches have always had (n + 256) / 256 blocks)
         HIP_TRY(hipMemsetAsync(c64.p, 0, (n_he + 1) * 8, c->stream));
         hipLaunchKernelGGL(k_widen_u32, dim3(egrid), dim3(256), 0, c->stream, (const uint32_t*)counts.p, n_he, (uint64_t*)c64.p);
         HIP_TRY(hipGetLastError());
@@ -578,20 +572,19 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
         if (h_first[n_he] != n_pairs) return fail(DFK_E_HIP, "paths index: the per-edge counts add up to %llu, the paths hold %llu entries", (unsigned long long)h_first[n_he], (unsigned long long)n_pairs);
         c->release(c64); c->release(first); c->release(d_inv);
         // ---- the files' fixed parts
-        const uint64_t var_tab = 24 + 8 * n_pairs, file_size = var_tab + 8 * (n_he + 1);
+        const FeudalLayout lay = feudal_layout(n_he, 16, 8, 8 * n_pairs);
         const std::string path = dir + "/a.paths.inv";
         if (!dir.empty()) {
             // a.paths.inv: feudal file of SerfVec<unsigned long> (IncrementalWriter<ULongVec>, :76): control block {n, 1, 0, 16, 8}, the
             // ids, n+1 absolute offsets
-            struct { uint32_t n; uint8_t flags, szFixed, szX, szA; uint64_t varTab, fixedOff; } h{(uint32_t)n_he, 1, 0, 16, 8, var_tab, file_size};
             // (not truncated either: pages made beforehand are used, the size is set here -- and when they were ALL there, the lists
             // go in through a mapping, every lane at once: FileMap)
             fd = open(path.c_str(), O_RDWR | O_CREAT, 0666);
             if (fd < 0) return fail(DFK_E_ARG, "cannot open %s", path.c_str());
             { struct stat sb; had = fstat(fd, &sb) == 0 ? (uint64_t)sb.st_size : 0; }
-            if (!(pwrite(fd, &h, 24, 0) == 24 && ftruncate(fd, (off_t)file_size) == 0)) return fail(DFK_E_ARG, "short write to %s", path.c_str());
+            if (!(pwrite(fd, &lay.head, 24, 0) == 24 && ftruncate(fd, (off_t)lay.file_size) == 0)) return fail(DFK_E_ARG, "short write to %s", path.c_str());
             std::vector<FilePiece> pieces;
-            for (uint64_t o = 0; o < 8 * (n_he + 1); o += XFER_CHUNK) pieces.push_back(FilePiece{(const char*)eo.p + o, std::min<uint64_t>(XFER_CHUNK, 8 * (n_he + 1) - o), var_tab + o});
+            append_pieces(pieces, (const char*)eo.p, 8 * (n_he + 1), lay.var_tab, XFER_CHUNK);
             if (write_pieces(c, fd, pieces)) return fail(DFK_E_ARG, "short write to %s", path.c_str());
             // a.countsb: BinaryWriter::writeFile of vec<vec<int>> with one row (:64,131)
             std::vector<int32_t> hc(n_he);
@@ -601,14 +594,12 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
         }
         c->release(eo); c->release(csb); c->release(counts);
         // ---- the lists, a range of edges at a time: 24 bytes per entry while a range is sorted and widened
-        uint64_t cap = std::min<uint64_t>((1ull << 31) - 1, std::max<uint64_t>(1ull << 20, c->largest_allocatable() / 2 / 24));
-        if (const char* e = getenv("DFK_PIDX_RANGE_PAIRS")) cap = std::max<uint64_t>(1, (uint64_t)atoll(e));
+        const uint64_t cap = pidx_range_cap(c->largest_allocatable(), sw.pidx_range_pairs);
         uint32_t n_ranges = 0;
         for (uint64_t e0 = 0; e0 < n_he;) {
-            uint64_t e1 = e0 + 1;
-            while (e1 < n_he && h_first[e1 + 1] - h_first[e0] <= cap) ++e1;
-            const uint64_t n_r = h_first[e1] - h_first[e0];
-            if (n_r >= (1ull << 32)) return fail(DFK_E_ARG, "edge %llu alone is on %llu reads: a range of the paths index sorts 32-bit positions", (unsigned long long)e0, (unsigned long long)n_r);
+            const PidxRange range = pidx_next_range(h_first.data(), n_he, e0, cap);
+            const uint64_t e1 = range.e1, n_r = range.n;
+            if (!range.ok) return fail(DFK_E_ARG, "edge %llu alone is on %llu reads: a range of the paths index sorts 32-bit positions", (unsigned long long)e0, (unsigned long long)n_r);
             ++n_ranges;
             if (n_r) {
                 DevBuf k[2], v[2], var;
@@ -617,7 +608,7 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
                 if (tail && !whole) { c->release(tail->var); tail = nullptr; }      // (several ranges: each is written before the next is sorted)
                 uint64_t pair_base = 0;
                 for (const PathBatch& b : P->batches) {
-                    const unsigned grid = (unsigned)std::min<uint64_t>((b.n + 256) / 256, 32ull * cus);
+                    const unsigned grid = grid_256(b.n + 1, cus);      // (+ 1: as egrid)
                     if (whole) {                                            // every entry of every read: its place follows from the elements' offsets
                         hipLaunchKernelGGL(k_pidx_range_pairs, dim3(grid), dim3(256), 0, c->stream, (const uint32_t*)b.var.p, (const uint32_t*)b.elem_off.p, b.n, b.r0, b.var_bytes, 0u, (uint32_t)n_he,
                                            (const uint64_t*)nullptr, pair_base, (uint32_t*)k[0].p, (uint32_t*)v[0].p);
@@ -642,21 +633,22 @@ int paths_index_write(dfk_ctx* c, HostGraph* G, PathState* P, const std::string&
                 if (pair_base != n_r) return fail(DFK_E_HIP, "paths index: %llu entries listed for edges [%llu, %llu), the counts say %llu", (unsigned long long)pair_base, (unsigned long long)e0, (unsigned long long)e1, (unsigned long long)n_r);
                 // stable sort by edge: read ids stay ascending inside an edge (ParallelSort of (edge, read) pairs, :87)
                 int cur = 0;
-                if ((rc = radix_sort_pairs(c, k, v, n_r, std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(2, e1 - e0))), &cur))) return rc;
+                if ((rc = radix_sort_pairs(c, k, v, n_r, pidx_key_bits(e1 - e0), &cur))) return rc;
                 c->release(k[0]); c->release(k[1]); c->release(v[cur ^ 1]);
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint32_t>), dim3((unsigned)std::min<uint64_t>((n_r + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream,
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint32_t>), dim3(grid_256(n_r, cus)), dim3(256), 0, c->stream,
                                    (const uint32_t*)v[cur].p, n_r, 0x1111ull + h_first[e0], d);
                 HIP_TRY(hipGetLastError());
                 if (!dir.empty()) {
                     if (!tail && (rc = c->alloc(var, n_r * 8, "a.paths.inv data", Place::Low))) return rc;
                     uint64_t* wide = (uint64_t*)(tail ? tail->var.p : var.p);
-                    hipLaunchKernelGGL(k_widen_u32, dim3((unsigned)std::min<uint64_t>((n_r + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream, (const uint32_t*)v[cur].p, n_r, wide);
+                    hipLaunchKernelGGL(k_widen_u32, dim3(grid_256(n_r, cus)), dim3(256), 0, c->stream, (const uint32_t*)v[cur].p, n_r, wide);
                     HIP_TRY(hipGetLastError());
                     HIP_TRY(hipStreamSynchronize(c->stream));
+                    const PidxMap pm = pidx_map(had, lay.var_tab, h_first[e0], n_r);
+                    const bool mapped = pm.mapped;          // the lists' pages exist: through a mapping
+                    const uint64_t m_lo = pm.lo, m_hi = pm.hi;
                     std::vector<FilePiece> pieces;
-                    for (uint64_t o = 0; o < 8 * n_r; o += XFER_CHUNK) pieces.push_back(FilePiece{(const char*)wide + o, std::min<uint64_t>(XFER_CHUNK, 8 * n_r - o), 24 + 8 * h_first[e0] + o});
-                    const bool mapped = had >= var_tab;     // the lists' pages exist: through a mapping
-                    const uint64_t m_lo = 24 + 8 * h_first[e0], m_hi = m_lo + 8 * n_r;
+                    append_pieces(pieces, (const char*)wide, 8 * n_r, m_lo, XFER_CHUNK);
                     if (tail) {
                         tail->fd = fd; fd = -1;
                         const int dev = c->device;
@@ -716,21 +708,16 @@ int dups_write(dfk_ctx* c, PathState* P, const std::string& path, uint64_t* n_ma
         HIP_TRY(hipMemsetAsync(dup.p, 0, std::max<uint64_t>(1, n_pairs), c->stream));
         HIP_TRY(hipMemsetAsync(d_bad.p, 0, 16, c->stream));
         // as many passes as the free HBM asks for: a pass's table holds the keys dealt to it at load <= 0.5
-        uint32_t n_pass = 1;
-        uint64_t slots = 0;
-        // (a table as large as the room allows is not the fastest: at configs[1] two passes over 69 GB took 3.0 s where four
-        // over 34 GB take 0.3 -- the larger one needed a chunk the driver had to produce first)
-        for (;; n_pass *= 2) {
-            slots = 1ull << std::max<uint32_t>(10, ceil_log2(2 * (P->n_placed / n_pass + P->n_placed / (4 * n_pass) + 1024)));   // (+25 %: the deal is by hash)
-            if (16 * slots <= c->largest_allocatable() / 2 || n_pass >= 1024) break;
-        }
+        const DupPlan plan = plan_dups(P->n_placed, c->largest_allocatable(), path_switches().dup_passes);
+        const uint32_t n_pass = plan.n_pass;
+        const uint64_t slots = plan.slots;
         if ((rc = c->alloc(tk, slots * 8, "duplicate keys", Place::Low)) || (rc = c->alloc(tb, slots * 8, "duplicate winners", Place::Low))) return rc;
         for (uint32_t pass = 0; pass < n_pass; ++pass) {
             hipLaunchKernelGGL(k_fill_u64, dim3(4096), dim3(256), 0, c->stream, (uint64_t*)tk.p, slots, ~0ull);
             HIP_TRY(hipMemsetAsync(tb.p, 0, slots * 8, c->stream));
             for (int markp = 0; markp < 2; ++markp)
                 for (const PathBatch& b : P->batches) {
-                    const unsigned grid = (unsigned)std::min<uint64_t>((b.n + 255) / 256, 32ull * cus);
+                    const unsigned grid = grid_256(b.n, cus);
                     if (!markp) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dup_pass<false>), dim3(grid), dim3(256), 0, c->stream, (const uint32_t*)b.var.p, (const uint32_t*)b.elem_off.p, b.n, b.r0,
                                                    b.var_bytes, (const uint32_t*)P->digest.p, (unsigned long long*)tk.p, (unsigned long long*)tb.p, slots - 1, n_pass, pass,
                                                    (uint8_t*)dup.p, (unsigned int*)d_bad.p);
@@ -748,7 +735,7 @@ int dups_write(dfk_ctx* c, PathState* P, const std::string& path, uint64_t* n_ma
         {   // dfk_paths_digest: which pairs are marked, and how many
             DevBuf dg; if ((rc = c->alloc(dg, 32, "dup digest", Place::Low))) return rc;
             HIP_TRY(hipMemsetAsync(dg.p, 0, 32, c->stream));
-            if (n_pairs) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint8_t>), dim3((unsigned)std::min<uint64_t>((n_pairs + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream,
+            if (n_pairs) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint8_t>), dim3(grid_256(n_pairs, cus)), dim3(256), 0, c->stream,
                                             (const uint8_t*)dup.p, n_pairs, 0x4444ull, (unsigned long long*)dg.p);
             HIP_TRY(hipGetLastError());
             uint64_t h[4] = {};
@@ -765,7 +752,7 @@ int dups_write(dfk_ctx* c, PathState* P, const std::string& path, uint64_t* n_ma
             struct { char magic[8]; uint64_t n; } hd{{'B', 'I', 'N', 'W', 'R', 'I', 'T', 'E'}, n_pairs};
             rc = pwrite(fd, &hd, 16, 0) == 16 ? 0 : fail(DFK_E_ARG, "short write to %s", path.c_str());
             std::vector<FilePiece> pieces;
-            for (uint64_t o = 0; o < n_pairs; o += XFER_CHUNK) pieces.push_back(FilePiece{(const char*)dup.p + o, std::min<uint64_t>(XFER_CHUNK, n_pairs - o), 16 + o});
+            append_pieces(pieces, (const char*)dup.p, n_pairs, 16, XFER_CHUNK);
             if (!rc && write_pieces(c, fd, pieces)) rc = fail(DFK_E_ARG, "short write to %s", path.c_str());
             if (close(fd) != 0 && !rc) rc = fail(DFK_E_ARG, "short write to %s", path.c_str());
             if (rc) return rc;
@@ -792,7 +779,7 @@ int paths_verify_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in,
     DevBuf ctr; int rc = c->alloc(ctr, 8 * PV_N + 8, "verify counters", Place::Low); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(ctr.p, 0, 8 * PV_N + 8, c->stream));
     const unsigned cus = (unsigned)c->prop.multiProcessorCount;
-    const unsigned g = (unsigned)std::min<uint64_t>((in.n_reads + 255) / 256, 32ull * cus);
+    const unsigned g = grid_256(in.n_reads, cus);
     hipLaunchKernelGGL(k_check_tables, dim3(std::max(1u, g)), dim3(256), 0, c->stream, in.base_off, in.packed_bytes, in.read_len, (const uint64_t*)nullptr, 0ull, in.n_reads,
                        (unsigned int*)((char*)ctr.p + 8 * PV_N));
     const PartTable pt = part_table_of(c);
@@ -802,7 +789,7 @@ int paths_verify_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in,
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (bad) { c->release(ctr); return fail(DFK_E_INPUT, "verify: the reads' offset table is not monotone, runs past its array, or leaves a read fewer bytes than its bases need"); }
     for (const PathBatch& b : P->batches)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_verify<K>), dim3((unsigned)std::min<uint64_t>((b.n + 255) / 256, 64ull * cus)), dim3(256), 0, c->stream, pt,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_verify<K>), dim3(grid_256(b.n, cus, 64)), dim3(256), 0, c->stream, pt,
                            (const uint32_t*)G->d_index.p, G->index_slots, pg, in.packed, in.base_off, in.read_len,
                            (const uint32_t*)b.var.p, (const uint32_t*)b.elem_off.p, b.n, b.r0, b.var_bytes, (unsigned long long*)ctr.p);
     HIP_TRY(hipGetLastError());
@@ -864,10 +851,10 @@ int bads_write(dfk_ctx* c, PathState* P, const char* path, bool part, uint64_t f
         if ((rc = c->alloc(marks, std::max<uint64_t>(1, n_pairs), "bad-pair marks", Place::Low)) || (rc = c->alloc(dg, 64, "bad digest", Place::Low))) return rc;
         HIP_TRY(hipMemsetAsync(dg.p, 0, 64, c->stream));
         if (n_pairs) {
-            const unsigned grid = (unsigned)std::min<uint64_t>((n_pairs + 255) / 256, 32ull * cus);
+            const unsigned grid = grid_256(n_pairs, cus);
             hipLaunchKernelGGL(k_bad_marks, dim3(grid), dim3(256), 0, c->stream, (const uint16_t*)P->bad_sums.p, n_pairs, (uint8_t*)marks.p);
             // over reads of h(whole-set read id, sum); the marks' plain sum is their number
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint16_t>), dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint16_t>), dim3(grid_256(n, cus)), dim3(256), 0, c->stream,
                                (const uint16_t*)P->bad_sums.p, n, 0x5555ull + first_read, (unsigned long long*)dg.p);
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint8_t>), dim3(grid), dim3(256), 0, c->stream, (const uint8_t*)marks.p, n_pairs, 0x6666ull + first_pair, (unsigned long long*)dg.p + 4);
             HIP_TRY(hipGetLastError());
@@ -885,7 +872,7 @@ int bads_write(dfk_ctx* c, PathState* P, const char* path, bool part, uint64_t f
         if (!rc && part && ftruncate(fd, (off_t)(16 + in_file)) != 0) rc = fail(DFK_E_ARG, "cannot size %s", path);      // every rank: the same size
         if (!rc) {
             std::vector<FilePiece> pieces;
-            for (uint64_t o = 0; o < n_pairs; o += XFER_CHUNK) pieces.push_back(FilePiece{(const char*)marks.p + o, std::min<uint64_t>(XFER_CHUNK, n_pairs - o), 16 + first_pair + o});
+            append_pieces(pieces, (const char*)marks.p, n_pairs, 16 + first_pair, XFER_CHUNK);
             if (write_pieces(c, fd, pieces)) rc = fail(DFK_E_ARG, "short write to %s", path);
         }
         if (close(fd) != 0 && !rc) rc = fail(DFK_E_ARG, "short write to %s", path);
@@ -998,9 +985,9 @@ int dfk_paths_write(dfk_ctx* c, const char* path)
     HIP_TRY(hipSetDevice(c->device));
     // feudal file (feudal/FeudalControlBlock.h:159-165, FeudalFileWriter.cc:26-121): control block | variable data |
     // n+1 absolute offsets | no fixed data (ReadPath keeps none outside the variable part)
-    const uint64_t n = P->n_reads, var_tab = 24 + P->var_total, file_size = var_tab + 8 * (n + 1);
-    struct { uint32_t n; uint8_t flags, szFixed, szX, szA; uint64_t varTab, fixedOff; } h{(uint32_t)n, 1, 0, 24, 4, var_tab, file_size};
-    static_assert(sizeof h == 24, "feudal control block");
+    const uint64_t n = P->n_reads;
+    const FeudalLayout lay = feudal_layout(n, 24, 4, P->var_total);
+    const uint64_t var_tab = lay.var_tab;
     // (with dfk_paths_sink on this path the variable data is in the file already, or on its way: wait for it, add the rest)
     const bool streamed = P->sink && P->sink->path == path;
     if (P->sink && !streamed) return fail(DFK_E_STATE, "the paths are being written to %s (dfk_paths_sink): write that file first", P->sink->path.c_str());
@@ -1008,8 +995,8 @@ int dfk_paths_write(dfk_ctx* c, const char* path)
     if (streamed) { rc = sink_finish(P, &fd); if (rc) return rc; }
     else fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
     if (fd < 0) return fail(DFK_E_ARG, "cannot open %s", path);
-    rc = pwrite(fd, &h, 24, 0) == 24 ? 0 : fail(DFK_E_ARG, "short write to %s", path);
-    if (!rc && ftruncate(fd, (off_t)file_size) != 0) rc = fail(DFK_E_ARG, "cannot size %s", path);
+    rc = pwrite(fd, &lay.head, 24, 0) == 24 ? 0 : fail(DFK_E_ARG, "short write to %s", path);
+    if (!rc && ftruncate(fd, (off_t)lay.file_size) != 0) rc = fail(DFK_E_ARG, "cannot size %s", path);
     const uint64_t last = var_tab;                                            // the (n+1)-th offset: the end of the variable data
     if (!rc && pwrite(fd, &last, 8, (off_t)(var_tab + 8 * n)) != 8) rc = fail(DFK_E_ARG, "short write to %s", path);
     // The batches' data as it is; their elements' absolute file offsets are the 32-bit ones kept per read, widened in the
@@ -1018,10 +1005,8 @@ int dfk_paths_write(dfk_ctx* c, const char* path)
     if (!rc) {
         std::vector<FilePiece> pieces;
         for (const PathBatch& b : P->batches) {
-            if (!streamed)
-                for (uint64_t o = 0; o < b.var_bytes; o += XFER_CHUNK) pieces.push_back(FilePiece{(const char*)b.var.p + o, std::min<uint64_t>(XFER_CHUNK, b.var_bytes - o), b.file_base + o});
-            for (uint64_t o = 0; o < b.n * 4; o += XFER_CHUNK / 2)
-                pieces.push_back(FilePiece{(const char*)b.elem_off.p + o, std::min<uint64_t>(XFER_CHUNK / 2, b.n * 4 - o), var_tab + 8 * b.r0 + 2 * o, true, b.file_base});
+            if (!streamed) append_pieces(pieces, (const char*)b.var.p, b.var_bytes, b.file_base, XFER_CHUNK);
+            append_wide_pieces(pieces, (const char*)b.elem_off.p, b.n * 4, var_tab + 8 * b.r0, b.file_base, XFER_CHUNK);
         }
         rc = write_pieces(c, fd, pieces);
         if (rc) rc = fail(DFK_E_ARG, "short write to %s", path);

@@ -81,8 +81,6 @@ struct ShardPaths {                 // what the sharded steps keep between their
 };
 ShardPaths* shard_paths_of(PathState* P) { if (!P->shard) { P->shard = new ShardPaths; P->shard_free = [](void* p) { delete (ShardPaths*)p; }; } return (ShardPaths*)P->shard; }
 
-uint64_t edge_range_start(uint64_t n_he, uint32_t world, uint32_t r) { return (uint64_t)r * n_he / world; }
-
 } // namespace
 
 extern "C" {
@@ -105,23 +103,20 @@ int dfk_paths_write_part(dfk_ctx* c, const char* path, uint64_t first_read, uint
     const uint64_t n = P->n_reads;
     if (first_read + n > total_reads || var_before + P->var_total > var_total || total_reads >= (1ull << 32)) return fail(DFK_E_ARG, "this rank's paths do not fit the file described");
     HIP_TRY(hipSetDevice(c->device));
-    const uint64_t var_tab = 24 + var_total, file_size = var_tab + 8 * (total_reads + 1);
+    const FeudalLayout lay = feudal_layout(total_reads, 24, 4, var_total);
+    const uint64_t var_tab = lay.var_tab, file_size = lay.file_size;
     const int fd = open(path, O_WRONLY | O_CREAT, 0666);
     if (fd < 0) return fail(DFK_E_ARG, "cannot open %s", path);
     int rc = 0;
-    if (first_read == 0) {
-        struct { uint32_t n; uint8_t flags, szFixed, szX, szA; uint64_t varTab, fixedOff; } h{(uint32_t)total_reads, 1, 0, 24, 4, var_tab, file_size};
-        if (pwrite(fd, &h, 24, 0) != 24) rc = fail(DFK_E_ARG, "short write to %s", path);
-    }
+    if (first_read == 0 && pwrite(fd, &lay.head, 24, 0) != 24) rc = fail(DFK_E_ARG, "short write to %s", path);
     if (!rc && ftruncate(fd, (off_t)file_size) != 0) rc = fail(DFK_E_ARG, "cannot size %s", path);      // every rank: the same size
     if (!rc && first_read + n == total_reads && pwrite(fd, &var_tab, 8, (off_t)(var_tab + 8 * total_reads)) != 8) rc = fail(DFK_E_ARG, "short write to %s", path);
     if (!rc) {
         std::vector<FilePiece> pieces;
         for (const PathBatch& b : P->batches) {
             const uint64_t at = var_before + b.file_base;                        // (file_base counts from 24 within this rank's data)
-            for (uint64_t o = 0; o < b.var_bytes; o += XFER_CHUNK) pieces.push_back(FilePiece{(const char*)b.var.p + o, std::min<uint64_t>(XFER_CHUNK, b.var_bytes - o), at + o});
-            for (uint64_t o = 0; o < b.n * 4; o += XFER_CHUNK / 2)
-                pieces.push_back(FilePiece{(const char*)b.elem_off.p + o, std::min<uint64_t>(XFER_CHUNK / 2, b.n * 4 - o), var_tab + 8 * (first_read + b.r0) + 2 * o, true, at});
+            append_pieces(pieces, (const char*)b.var.p, b.var_bytes, at, XFER_CHUNK);
+            append_wide_pieces(pieces, (const char*)b.elem_off.p, b.n * 4, var_tab + 8 * (first_read + b.r0), at, XFER_CHUNK);
         }
         rc = write_pieces(c, fd, pieces);
         if (rc) rc = fail(DFK_E_ARG, "short write to %s", path);
@@ -157,26 +152,22 @@ int dfk_shard_pidx_pairs(dfk_ctx* c, uint32_t world, const void** d_pairs, uint6
         HIP_TRY(hipMemsetAsync(counts.p, 0, n_he * 4, c->stream));
         uint64_t pair_base = 0;
         for (const PathBatch& b : P->batches) {
-            hipLaunchKernelGGL(k_pidx_pairs, dim3((unsigned)std::min<uint64_t>((b.n + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream, (const uint32_t*)b.var.p,
+            hipLaunchKernelGGL(k_pidx_pairs, dim3(grid_256(b.n, cus)), dim3(256), 0, c->stream, (const uint32_t*)b.var.p,
                                (const uint32_t*)b.elem_off.p, b.n, b.r0 + (uint64_t)P->read_id0, b.var_bytes, pair_base, (uint32_t*)k[0].p, (uint32_t*)v[0].p, (uint32_t*)counts.p);
             pair_base += b.var_bytes / 4 - 2 * b.n;
         }
         HIP_TRY(hipGetLastError());
         if (pair_base != n_pairs) return fail(DFK_E_HIP, "paths index: %llu path entries listed, %llu counted", (unsigned long long)pair_base, (unsigned long long)n_pairs);
         int cur = 0;
-        if ((rc = radix_sort_pairs(c, k, v, n_pairs, std::max<uint32_t>(1, ceil_log2(n_he)), &cur))) return rc;
-        if (n_pairs) hipLaunchKernelGGL(k_pack_pairs, dim3((unsigned)std::min<uint64_t>((n_pairs + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream, (const uint32_t*)k[cur].p,
+        if ((rc = radix_sort_pairs(c, k, v, n_pairs, pidx_key_bits(n_he), &cur))) return rc;
+        if (n_pairs) hipLaunchKernelGGL(k_pack_pairs, dim3(grid_256(n_pairs, cus)), dim3(256), 0, c->stream, (const uint32_t*)k[cur].p,
                                         (const uint32_t*)v[cur].p, n_pairs, (uint64_t*)S->pairs.p);
         HIP_TRY(hipGetLastError());
         std::vector<uint32_t> hc(n_he);
         HIP_TRY(hipMemcpyAsync(hc.data(), counts.p, n_he * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         for (uint64_t e = 0; e < n_he; ++e) counts_host[e] = hc[e];
-        for (uint32_t r = 0; r < world; ++r) {
-            uint64_t s = 0;
-            for (uint64_t e = edge_range_start(n_he, world, r); e < edge_range_start(n_he, world, r + 1); ++e) s += hc[e];
-            send_counts[r] = s;
-        }
+        shard_send_counts(hc.data(), n_he, world, send_counts);
         return 0;
     };
     try { rc = body(); } catch (const std::runtime_error& e) { rc = fail(DFK_E_HIP, "%s", e.what()); }
@@ -199,8 +190,7 @@ int dfk_shard_pidx_write(dfk_ctx* c, uint32_t world, uint32_t rank, const void* 
     const uint64_t n_he = G->he.size(), e0 = edge_range_start(n_he, world, rank), e1 = edge_range_start(n_he, world, rank + 1), ne = e1 - e0;
     ShardPaths* S = shard_paths_of(P);
     c->release(S->pairs);                                                  // (sent: the room goes to the merge)
-    std::vector<uint64_t> first(n_he + 1, 0);
-    for (uint64_t e = 0; e < n_he; ++e) first[e + 1] = first[e] + counts_global[e];
+    const std::vector<uint64_t> first = prefix_sums(counts_global, n_he);
     const uint64_t total = first[n_he];
     if (first[e1] - first[e0] != n_in) return fail(DFK_E_HIP, "paths index: rank %u received %llu entries for its edges, the counts say %llu", rank, (unsigned long long)n_in,
                                                    (unsigned long long)(first[e1] - first[e0]));
@@ -214,11 +204,11 @@ int dfk_shard_pidx_write(dfk_ctx* c, uint32_t world, uint32_t rank, const void* 
         if ((rc = c->alloc(cnt, std::max<uint64_t>(1, ne) * 4, "reads per edge", Place::Low)) || (rc = c->alloc(d_bad, 16, "index check", Place::Low))) return rc;
         HIP_TRY(hipMemsetAsync(cnt.p, 0, std::max<uint64_t>(1, ne) * 4, c->stream));
         HIP_TRY(hipMemsetAsync(d_bad.p, 0, 16, c->stream));
-        if (n_in) hipLaunchKernelGGL(k_unpack_pairs, dim3((unsigned)std::min<uint64_t>((n_in + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream, (const uint64_t*)d_pairs_in, n_in,
+        if (n_in) hipLaunchKernelGGL(k_unpack_pairs, dim3(grid_256(n_in, cus)), dim3(256), 0, c->stream, (const uint64_t*)d_pairs_in, n_in,
                                      (uint32_t)e0, (uint32_t)e1, (uint32_t*)k[0].p, (uint32_t*)v[0].p, (uint32_t*)cnt.p, (unsigned int*)d_bad.p);
         HIP_TRY(hipGetLastError());
         int cur = 0;
-        if ((rc = radix_sort_pairs(c, k, v, n_in, std::max<uint32_t>(1, ceil_log2(std::max<uint64_t>(2, ne))), &cur))) return rc;
+        if ((rc = radix_sort_pairs(c, k, v, n_in, pidx_key_bits(ne), &cur))) return rc;
         std::vector<uint32_t> hc(ne);
         unsigned bad = 0;
         if (ne) HIP_TRY(hipMemcpyAsync(hc.data(), cnt.p, ne * 4, hipMemcpyDeviceToHost, c->stream));
@@ -228,18 +218,18 @@ int dfk_shard_pidx_write(dfk_ctx* c, uint32_t world, uint32_t rank, const void* 
         for (uint64_t e = 0; e < ne; ++e) if (hc[e] != counts_global[e0 + e]) return fail(DFK_E_HIP, "paths index: edge %llu received %u reads, the counts say %llu", (unsigned long long)(e0 + e), hc[e], (unsigned long long)counts_global[e0 + e]);
         c->release(k[0]); c->release(k[1]); c->release(v[cur ^ 1]);
         if ((rc = c->alloc(var, np1 * 8, "a.paths.inv data", Place::Low))) return rc;
-        if (n_in) hipLaunchKernelGGL(k_widen_u32, dim3((unsigned)std::min<uint64_t>((n_in + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream, (const uint32_t*)v[cur].p, n_in, (uint64_t*)var.p);
+        if (n_in) hipLaunchKernelGGL(k_widen_u32, dim3(grid_256(n_in, cus)), dim3(256), 0, c->stream, (const uint32_t*)v[cur].p, n_in, (uint64_t*)var.p);
         HIP_TRY(hipGetLastError());
         {   // digests of this rank's share (dfk_paths_digest; the caller adds / xors the ranks' words): positions and edges are the whole file's
             DevBuf dg, d_first;
             if ((rc = c->alloc(dg, 128, "index digest", Place::Low)) || (rc = c->alloc(d_first, (ne + 1) * 8, "list starts", Place::Low))) return rc;
             HIP_TRY(hipMemsetAsync(dg.p, 0, 128, c->stream));
-            const uint64_t n_first = ne + (rank + 1 == world ? 1 : 0);      // (the last rank also holds the end of the last list)
+            const uint64_t n_first = shard_table_entries(ne, world, rank);   // (the last rank also holds the end of the last list)
             HIP_TRY(hipMemcpyAsync(d_first.p, first.data() + e0, n_first * 8, hipMemcpyHostToDevice, c->stream));
             unsigned long long* d = (unsigned long long*)dg.p;
-            if (n_in) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint32_t>), dim3((unsigned)std::min<uint64_t>((n_in + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream,
+            if (n_in) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint32_t>), dim3(grid_256(n_in, cus)), dim3(256), 0, c->stream,
                                          (const uint32_t*)v[cur].p, n_in, 0x1111ull + first[e0], d);
-            if (n_first) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint64_t>), dim3((unsigned)std::min<uint64_t>((n_first + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream,
+            if (n_first) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint64_t>), dim3(grid_256(n_first, cus)), dim3(256), 0, c->stream,
                                             (const uint64_t*)d_first.p, n_first, 0x2222ull + e0, d + 4);
             HIP_TRY(hipGetLastError());
             uint64_t h[16] = {};
@@ -251,24 +241,20 @@ int dfk_shard_pidx_write(dfk_ctx* c, uint32_t world, uint32_t rank, const void* 
         }
         // this rank's range of a.paths.inv: the lists of edges [e0, e1) and their entries of the offset table
         const std::string path = std::string(dir) + "/a.paths.inv";
-        const uint64_t var_tab = 24 + 8 * total, file_size = var_tab + 8 * (n_he + 1);
+        const FeudalLayout lay = feudal_layout(n_he, 16, 8, 8 * total);
         const int fd = open(path.c_str(), O_WRONLY | O_CREAT, 0666);
         if (fd < 0) return fail(DFK_E_ARG, "cannot open %s", path.c_str());
         int wrc = 0;
-        if (rank == 0) {
-            struct { uint32_t n; uint8_t flags, szFixed, szX, szA; uint64_t varTab, fixedOff; } h{(uint32_t)n_he, 1, 0, 16, 8, var_tab, file_size};
-            if (pwrite(fd, &h, 24, 0) != 24) wrc = fail(DFK_E_ARG, "short write to %s", path.c_str());
-        }
-        if (!wrc && ftruncate(fd, (off_t)file_size) != 0) wrc = fail(DFK_E_ARG, "cannot size %s", path.c_str());
+        if (rank == 0 && pwrite(fd, &lay.head, 24, 0) != 24) wrc = fail(DFK_E_ARG, "short write to %s", path.c_str());
+        if (!wrc && ftruncate(fd, (off_t)lay.file_size) != 0) wrc = fail(DFK_E_ARG, "cannot size %s", path.c_str());
         if (!wrc) {
-            std::vector<uint64_t> eo(ne + 1);
-            for (uint64_t e = 0; e <= ne; ++e) eo[e] = 24 + 8 * first[e0 + e];
-            const uint64_t n_eo = ne + (rank + 1 == world ? 1 : 0);
-            if (n_eo && pwrite(fd, eo.data(), 8 * n_eo, (off_t)(var_tab + 8 * e0)) != (ssize_t)(8 * n_eo)) wrc = fail(DFK_E_ARG, "short write to %s", path.c_str());
+            const std::vector<uint64_t> eo = shard_table_slice(first, e0, e1);
+            const uint64_t n_eo = shard_table_entries(ne, world, rank);
+            if (n_eo && pwrite(fd, eo.data(), 8 * n_eo, (off_t)(lay.var_tab + 8 * e0)) != (ssize_t)(8 * n_eo)) wrc = fail(DFK_E_ARG, "short write to %s", path.c_str());
         }
         if (!wrc) {
             std::vector<FilePiece> pieces;
-            for (uint64_t o = 0; o < 8 * n_in; o += XFER_CHUNK) pieces.push_back(FilePiece{(const char*)var.p + o, std::min<uint64_t>(XFER_CHUNK, 8 * n_in - o), 24 + 8 * first[e0] + o});
+            append_pieces(pieces, (const char*)var.p, 8 * n_in, 24 + 8 * first[e0], XFER_CHUNK);
             wrc = write_pieces(c, fd, pieces);
             if (wrc) wrc = fail(DFK_E_ARG, "short write to %s", path.c_str());
         }
@@ -317,7 +303,7 @@ int dfk_shard_dup_keys(dfk_ctx* c, uint32_t world, const void** d_items, uint64_
     HIP_TRY(hipMemsetAsync(d_bad.p, 0, 16, c->stream));
     auto sweep = [&](bool place) {
         for (const PathBatch& b : P->batches) {
-            const unsigned grid = (unsigned)std::min<uint64_t>((b.n + 255) / 256, 32ull * cus);
+            const unsigned grid = grid_256(b.n, cus);
             if (!place) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dup_items<false>), dim3(grid), dim3(256), 0, c->stream, (const uint32_t*)b.var.p, (const uint32_t*)b.elem_off.p, b.n, b.r0, b.var_bytes,
                                            (const uint32_t*)P->digest.p, (uint64_t)P->read_id0, world, (unsigned long long*)cur.p, (DupItem*)nullptr, (uint32_t*)nullptr, (unsigned int*)d_bad.p);
             else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dup_items<true>), dim3(grid), dim3(256), 0, c->stream, (const uint32_t*)b.var.p, (const uint32_t*)b.elem_off.p, b.n, b.r0, b.var_bytes,
@@ -360,7 +346,7 @@ int dfk_shard_dup_answer(dfk_ctx* c, const void* d_items_in, uint64_t n_in, void
     hipLaunchKernelGGL(k_fill_u64, dim3(4096), dim3(256), 0, c->stream, (uint64_t*)tk.p, slots, ~0ull);
     HIP_TRY(hipMemsetAsync(tb.p, 0, slots * 8, c->stream));
     HIP_TRY(hipMemsetAsync(d_bad.p, 0, 16, c->stream));
-    const unsigned grid = (unsigned)std::min<uint64_t>((n_in + 255) / 256, 32ull * cus);
+    const unsigned grid = grid_256(n_in, cus);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dup_table<false>), dim3(grid), dim3(256), 0, c->stream, (const DupItem*)d_items_in, n_in, (unsigned long long*)tk.p, (unsigned long long*)tb.p, slots - 1, (uint8_t*)d_ans, (unsigned int*)d_bad.p);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dup_table<true>), dim3(grid), dim3(256), 0, c->stream, (const DupItem*)d_items_in, n_in, (unsigned long long*)tk.p, (unsigned long long*)tb.p, slots - 1, (uint8_t*)d_ans, (unsigned int*)d_bad.p);
     HIP_TRY(hipGetLastError());
@@ -389,8 +375,8 @@ int dfk_shard_dup_write(dfk_ctx* c, const void* d_ans_back, uint64_t n, const ch
     if ((rc = c->alloc(dup, std::max<uint64_t>(1, n_pairs), "duplicate marks", Place::Low)) || (rc = c->alloc(dg, 32, "dup digest", Place::Low))) return rc;
     HIP_TRY(hipMemsetAsync(dup.p, 0, std::max<uint64_t>(1, n_pairs), c->stream));
     HIP_TRY(hipMemsetAsync(dg.p, 0, 32, c->stream));
-    if (n) hipLaunchKernelGGL(k_dup_mark, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream, (const uint8_t*)d_ans_back, (const uint32_t*)S->src.p, n, (uint8_t*)dup.p);
-    if (n_pairs) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint8_t>), dim3((unsigned)std::min<uint64_t>((n_pairs + 255) / 256, 32ull * cus)), dim3(256), 0, c->stream,
+    if (n) hipLaunchKernelGGL(k_dup_mark, dim3(grid_256(n, cus)), dim3(256), 0, c->stream, (const uint8_t*)d_ans_back, (const uint32_t*)S->src.p, n, (uint8_t*)dup.p);
+    if (n_pairs) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_digest_seq<uint8_t>), dim3(grid_256(n_pairs, cus)), dim3(256), 0, c->stream,
                                     (const uint8_t*)dup.p, n_pairs, 0x4444ull + first_pair, (unsigned long long*)dg.p);
     HIP_TRY(hipGetLastError());
     std::vector<uint8_t> h(n_pairs);

@@ -1,7 +1,8 @@
 """The device arena and the pass planner (superplus_amd/csrc/dfk_arena.h) are host code that never touches device
 memory: they run here, on a CPU, against a backing store that only counts.  So do the decisions of the count stage's
 hot-bucket fallback (superplus_amd/csrc/dfk_fallback.h): plain arithmetic over instance counts.  And so does the plan of
-the counting scan (superplus_amd/csrc/dfk_scan_plan.h): plain arithmetic over read and byte counts."""
+the counting scan (superplus_amd/csrc/dfk_scan_plan.h): plain arithmetic over read and byte counts.  And so do the plans of
+the steps after the count -- pathing, the paths index, the duplicate marks (superplus_amd/csrc/dfk_paths_plan.h)."""
 import os
 import subprocess
 
@@ -45,3 +46,18 @@ def test_cpp_scan_plan(tmp_path, flags):
     subprocess.check_call(["g++", *flags, "-std=c++17", "-Wall", "-o", exe, os.path.join(root, "tests", "cpp", "test_scan_plan.cc")])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "FAILED" not in out.stdout and out.stdout.count(": ok") == 8, out.stdout + out.stderr
+
+
+@pytest.mark.parametrize("flags", [["-O1"], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]], ids=["plain", "sanitized"])
+def test_cpp_paths_plan(tmp_path, flags):
+    """tests/cpp/test_paths_plan.cc: the reads a pathing batch may hold, the k-mer filter's decision, a batch's room, reads,
+    need and scratch sizes, the feudal control block, the index's tail thread, range cap, ranges, key bits and mapping, the
+    duplicate table's passes, the ranks' edge ranges -- against tables recorded from the code before it moved into the header
+    (tests/cpp/paths_plan_expected.h: K = 40, 48, 60, both sides of every threshold, the default benchmark's figures among
+    them), the properties of batches, ranges, passes, file pieces and the sharded index over 10^4 seeded random cases each, and
+    the batch planner replayed over 6000 reads in 24 batches.  A stand-alone program, also under the sanitizers."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "test_paths_plan")
+    subprocess.check_call(["g++", *flags, "-std=c++17", "-Wall", "-o", exe, os.path.join(root, "tests", "cpp", "test_paths_plan.cc")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "FAILED" not in out.stdout and out.stdout.count(": ok") == 16, out.stdout + out.stderr

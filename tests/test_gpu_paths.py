@@ -254,3 +254,101 @@ def test_quality_histogram_of_the_kept_reads(per_base):
     short = max(1, max_len - 7)                                            # positions from max_len on are left out
     assert np.array_equal(d.qual_hist(short), want[:, :short])
     d.close()
+
+
+# The trace is switched on when the library is loaded (DFK_TRACE), so the runs below happen in a fresh child process: one
+# child per fixture does every setting in turn, announces each on the trace's own stream and reports what it found as JSON.
+_CHILD = r"""
+import json, os, sys
+from tests.test_gpu_paths import KW
+from tests.test_paths_oracle import load_reads
+from superplus_amd.dfk import Dfk
+golden, which, case, K, out_dir, settings = sys.argv[1], sys.argv[2], sys.argv[3], int(sys.argv[4]), sys.argv[5], json.loads(sys.argv[6])
+rs = load_reads(golden, which)
+kw = dict(KW[case]); kw.pop("nobc", None)
+res = []
+for i, env in enumerate(settings):
+    for k in ("DFK_PATH_BATCH_READS", "DFK_DUP_PASSES", "DFK_PATH_SLOTS", "DFK_NO_FILTER"): os.environ.pop(k, None)
+    os.environ.update(env)
+    sys.stderr.write(f"[test] setting {i}\n"); sys.stderr.flush()
+    d = Dfk(K=K, **kw)
+    d.count(rs["packed"], rs["base_off"], rs["read_len"], rs["pq_bytes"], rs["pq_off"], rs["bc"])
+    d.graph_build()
+    out = os.path.join(out_dir, str(i)); os.makedirs(out)
+    if "DFK_PATH_SLOTS" in env: d.paths_sink(os.path.join(out, "a.paths"))
+    d.paths_build(rs["packed"], rs["base_off"], rs["read_len"], rs["pq_bytes"], rs["pq_off"])
+    d.paths_write(os.path.join(out, "a.paths"))
+    verify = d.paths_verify(rs["packed"], rs["base_off"], rs["read_len"])
+    d.paths_index_write(out)
+    marked = d.dups_write(os.path.join(out, "a.dup"))
+    same = {f: open(os.path.join(out, f), "rb").read() == open(os.path.join(golden, case, f), "rb").read()
+            for f in ("a.paths", "a.paths.inv", "a.countsb", "a.dup")}
+    res.append(dict(same=same, verify=verify, digest=d.paths_digest(), marked=marked))
+    d.close()
+print(json.dumps(res))
+"""
+
+
+def run_settings(golden_dir, tmp_path, which, case, K, settings):
+    """-> per setting: what the child reports, with the trace lines of that setting under "trace" """
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, "-c", _CHILD, str(golden_dir), which, case, str(K), str(tmp_path), json.dumps(settings)],
+                       cwd=root, env=dict(os.environ, DFK_TRACE="1"), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    res = json.loads(p.stdout.strip().splitlines()[-1])
+    chunks = p.stderr.split("[test] setting ")[1:]
+    assert len(chunks) == len(res) == len(settings)
+    for r, ch in zip(res, chunks): r["trace"] = ch
+    return res
+
+
+def traced(trace, pattern):
+    import re
+    m = re.findall(pattern, trace)
+    assert len(m) == 1, (pattern, trace[-2000:])
+    return int(m[0])
+
+
+@pytest.mark.parametrize("two_slots", [False, True], ids=["slots12", "slots2_nofilter_sink"])
+def test_pathing_in_batches_writes_the_same_files(golden_dir, tmp_path, two_slots):
+    """DFK_PATH_BATCH_READS cuts the pathing of the 6000 reads of `frag` into 24 batches of 257 (a 256-thread block and one
+    read) and into 6 of 1001 (odd: mates in different batches): a.paths, a.paths.inv, a.countsb and a.dup are the reference's
+    byte for byte, the verifier's counters and every digest word are those of the one batch the reads make by default.  With two
+    slots a read and no filter, batches are done again with all slots and a.paths goes through the sink."""
+    from tests.test_verify_oracle import EXPECT
+    from superplus_amd.dfk import VERIFY
+    extra = dict(DFK_PATH_SLOTS="2", DFK_NO_FILTER="1") if two_slots else dict()
+    res = run_settings(golden_dir, tmp_path, "frag", "graph_frag_k48", 48,
+                       [dict(extra), dict(extra, DFK_PATH_BATCH_READS="257"), dict(extra, DFK_PATH_BATCH_READS="1001")])
+    for r, batches in zip(res, (1, 24, 6)):
+        print(r["same"], r["verify"], traced(r["trace"], r"paths: .* (\d+) batches"))
+        assert all(r["same"].values()), r["same"]
+        assert [r["verify"][k] for k in VERIFY] == EXPECT["graph_frag_k48"]
+        assert traced(r["trace"], r"paths: .* (\d+) batches") == batches
+        if two_slots: assert "the batch again with all" in r["trace"]
+    assert res[0]["digest"] == res[1]["digest"] == res[2]["digest"] and res[0]["marked"] == res[1]["marked"] == res[2]["marked"]
+
+
+def test_pathing_in_batches_at_k60(golden_dir, tmp_path):
+    """The other template instance and the zoo's odd-cycle paths: 20624 reads at K=60 in 6 batches of 4099, two slots a read."""
+    from tests.test_verify_oracle import EXPECT
+    from superplus_amd.dfk import VERIFY
+    r, = run_settings(golden_dir, tmp_path, "zoo", "graph_zoo_k60", 60, [dict(DFK_PATH_SLOTS="2", DFK_NO_FILTER="1", DFK_PATH_BATCH_READS="4099")])
+    print(r["same"], r["verify"])
+    assert all(r["same"].values()), r["same"]
+    assert [r["verify"][k] for k in VERIFY] == EXPECT["graph_zoo_k60"]
+    assert traced(r["trace"], r"paths: .* (\d+) batches") == 6
+
+
+@pytest.mark.parametrize("which,case", [("frag", "graph_frag_k48"), ("pathy2", "graph_pathy2_k48")])
+def test_duplicates_marked_in_passes(golden_dir, tmp_path, which, case):
+    """DFK_DUP_PASSES deals the keys of MarkDups to 2 and to 8 tables filled one after the other (what short room makes it do at
+    full size): a.dup is the reference's byte for byte, its digest and the number of marked pairs those of the one pass."""
+    res = run_settings(golden_dir, tmp_path, which, case, 48, [dict(), dict(DFK_DUP_PASSES="2"), dict(DFK_DUP_PASSES="8")])
+    for r, passes in zip(res, (1, 2, 8)):
+        print(r["same"], r["digest"]["DUP_DIGEST"], r["digest"]["DUP_MARKED"], r["marked"])
+        assert r["same"]["a.dup"]
+        assert traced(r["trace"], r"duplicates: (\d+) pass\(es\)") == passes
+    words = [(r["digest"]["DUP_DIGEST"], r["digest"]["DUP_MARKED"], r["marked"]) for r in res]
+    assert words[0] == words[1] == words[2] and words[0][1] == words[0][2]
