@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DFK_ABI_VERSION 2
+#define DFK_ABI_VERSION 3
 #define DFK_MAX_MIN_BC 8u
 
 enum {
@@ -354,6 +354,57 @@ int dfk_hops_build_arrays(dfk_ctx* ctx, uint64_t n_edges, uint64_t n_vertices, c
 int dfk_hops_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_HOPS_WORDS] */);
 int dfk_hops_fetch(dfk_ctx* ctx, int32_t* pairs /* 2 per pair */, uint64_t cap, uint64_t* n_pairs);
 int dfk_hops_write(dfk_ctx* ctx, const char* path /* NULL = all but the file */, uint64_t* n_pairs, uint64_t* digest /* [2] or NULL */);
+
+/* ---- the third step of the patching stage: the subset of interest (StagePatch, 10X/runstages/RunStages.cc:208-254) ----
+ * From the edge pairs: in_pairs[x] for x in {first, second, inv[first], inv[second]} (:213-219); eoi, the marked edges ascending
+ * (:222-226); read_ids, both reads of every pair of which either read's path holds a marked edge, ascending (:228-241); and the two
+ * subsets the reference then loads from disk element by element: the ReadPaths of read_ids and the ULongVecs of eoi (:253-254).
+ * The rule, the plan and the files' layouts are stated in csrc/dfk_subset.h.  The qualities subset (:252) is not made: the ids file
+ * is what the reference's own SubsetMasterVec<PQVec>( qualp, read_ids ) needs.
+ *   dfk_subset_build    pairs NULL: the context's own dfk_hops_build* result (DFK_E_STATE without one).  Otherwise n_pairs x (i32, i32),
+ *                       e.g. read back from an a.hops; needs dfk_paths_build only, not DFK_F_MARK_BADS.  Marks, eoi, the sweep over
+ *                       the paths, the ids' number and digest, the entries per edge of interest.  Holds no device memory when it
+ *                       returns; eoi, the marks, a bit per pair and the lists' starts stay in host memory.
+ *   dfk_subset_build_arrays  the same stage on host arrays, for tests that choose graph, paths and pairs (dfk_hops_build_arrays'
+ *                       layout of first / edges).  The arrays do not outlive the call: with dir the four files are written there
+ *                       (NULL = none).  Its result is what dfk_subset_stats / _fetch serve until the next dfk_subset_build*;
+ *                       dfk_subset_write after it is DFK_E_STATE.  Leaves the context's count, graph and paths alone.
+ *   dfk_subset_stats    out[DFK_SUBSET_WORDS]: the counters below
+ *   dfk_subset_fetch    read_ids and eoi, ascending u64; a NULL buffer with cap 0 = that count alone; a buffer too small: DFK_E_ARG
+ *   dfk_subset_write    into dir (which must exist), all four or none:
+ *                         a.sub.ids, a.sub.eoi   "BINWRITE" | u64 n | n x u64 (vec<uint64_t> read_ids; vec<size_type> eoi, size_type =
+ *                                                size_t, system/Types.h:126)
+ *                         a.sub.paths            feudal ReadPathVec, a.paths' control block, n = ids: element k = the bytes of element
+ *                                                read_ids[k] of a.paths; absolute offsets
+ *                         a.sub.paths.inv        feudal VecULongVec, a.paths.inv's control block, n = eoi: element k = the bytes of
+ *                                                element eoi[k] of a.paths.inv
+ *                       streamed a batch of paths and a range of eoi ranks at a time (DFK_PIDX_RANGE_PAIRS forces small ranges):
+ *                       neither subset is ever whole on the device.
+ * Valid from dfk_paths_build until the paths are dropped, before or after dfk_paths_index_write / dfk_dups_write / dfk_bads_write;
+ * otherwise DFK_E_STATE.  A refused call changes nothing and an earlier result is still served: an edge id outside [0, E), an odd
+ * number of reads, a paths subset of 2^32 elements or more (a feudal file counts in 32 bits), one edge with 2^32 entries or more
+ * are DFK_E_ARG.  Not for the ranks of a sharded run. */
+#define DFK_SUBSET_WORDS 16
+#define DFK_SUBSET_N_EOI 0
+#define DFK_SUBSET_N_IDS 1
+#define DFK_SUBSET_PATH_ENTRIES 2    /* path entries of the reads in the subset */
+#define DFK_SUBSET_INDEX_ENTRIES 3   /* entries of the index subset */
+#define DFK_SUBSET_RANGES 4          /* ranges of eoi ranks the index subset is (the build: would be) written in */
+#define DFK_SUBSET_ONE_READ_ONLY 5   /* pairs taken through one read only */
+#define DFK_SUBSET_US 6              /* microseconds: the build call, */
+#define DFK_SUBSET_US_SWEEP 7        /* its marks, ranks and sweep, */
+#define DFK_SUBSET_US_GATHER 8       /* the ids and paths gather: the build's scans and ids, and the last write's copies, */
+#define DFK_SUBSET_US_INDEX 9        /* the index subset: the build's counts, and the last write's listing and sorting */
+#define DFK_SUBSET_IDS_SUM 10        /* sum and xor over positions i of read_ids of h(i, id) (k_digest_seq, salt 0x7777), */
+#define DFK_SUBSET_IDS_XOR 11
+#define DFK_SUBSET_EOI_SUM 12        /* ... and of eoi (salt 0x8888) */
+#define DFK_SUBSET_EOI_XOR 13
+int dfk_subset_build(dfk_ctx* ctx, const int32_t* pairs /* 2 per pair, or NULL */, uint64_t n_pairs);
+int dfk_subset_build_arrays(dfk_ctx* ctx, uint64_t n_edges, const int32_t* inv, uint64_t n_reads, const uint64_t* first /* [n_reads + 1] */, const int32_t* edges,
+                            const int32_t* pairs, uint64_t n_pairs, uint64_t reads_per_batch, const char* dir /* NULL = no files */);
+int dfk_subset_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_SUBSET_WORDS] */);
+int dfk_subset_fetch(dfk_ctx* ctx, uint64_t* ids, uint64_t ids_cap, uint64_t* n_ids, uint64_t* eoi, uint64_t eoi_cap, uint64_t* n_eoi);
+int dfk_subset_write(dfk_ctx* ctx, const char* dir);
 
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).

@@ -552,7 +552,7 @@ int main(int argc, char** argv)
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
         {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
-        {"HOPS", "False"}, {"ONE_GOOD", "True"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -575,6 +575,9 @@ int main(int argc, char** argv)
     // involution in one place.  Refused here, before a directory is made or a GPU is touched.
     if (truthy(a["HOPS"]) && (atoi(a["NUM_GPUS"].c_str()) > 1 || getenv("DF_FORCE_SHARDED") || (getenv("DF_TRANSPORT") && std::string(getenv("DF_TRANSPORT")) == "loopback")))
         give_up("HOPS=True runs on one GPU only (no NUM_GPUS > 1, DF_FORCE_SHARDED or DF_TRANSPORT=loopback): FindEdgePairs needs every read's path in one place");
+
+    // SUBSET=True (the subset of interest, a.<K>/a.sub.*) works from FindEdgePairs' pairs
+    if (truthy(a["SUBSET"]) && !truthy(a["HOPS"])) give_up("SUBSET=True needs HOPS=True: the subset of interest is taken from the edge pairs");
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -1009,6 +1012,15 @@ int main(int argc, char** argv)
                     printf("DF_HOPS {\"a.hops\": \"%016llx%016llx\", \"pairs\": %llu, \"m1\": %llu, \"m2\": %llu, \"m3\": %llu, \"host_edges\": %llu}\n", (unsigned long long)hd[0],
                            (unsigned long long)hd[1], (unsigned long long)n_hops, (unsigned long long)hs[DFK_HOPS_M1], (unsigned long long)hs[DFK_HOPS_M2],
                            (unsigned long long)hs[DFK_HOPS_M3], (unsigned long long)hs[DFK_HOPS_HOST_EDGES]);
+                    if (truthy(a["SUBSET"])) {                                  // the subset of interest (StagePatch, RunStages.cc:208-254): a.<K>/a.sub.*, after a.hops
+                        uint64_t ss[DFK_SUBSET_WORDS] = {};
+                        if (dfk_subset_build(ctx, nullptr, 0) || dfk_subset_write(ctx, dir.c_str()) || dfk_subset_stats(ctx, ss)) throw std::runtime_error(dfk_last_error());
+                        printf("subset is size %llu\n", (unsigned long long)ss[DFK_SUBSET_N_IDS]);     // RunStages.cc:246
+                        printf("DF_SUBSET {\"ids\": %llu, \"eoi\": %llu, \"path_entries\": %llu, \"index_entries\": %llu, \"ranges\": %llu, \"a.sub.ids\": \"%016llx%016llx\", \"a.sub.eoi\": \"%016llx%016llx\"}\n",
+                               (unsigned long long)ss[DFK_SUBSET_N_IDS], (unsigned long long)ss[DFK_SUBSET_N_EOI], (unsigned long long)ss[DFK_SUBSET_PATH_ENTRIES],
+                               (unsigned long long)ss[DFK_SUBSET_INDEX_ENTRIES], (unsigned long long)ss[DFK_SUBSET_RANGES], (unsigned long long)ss[DFK_SUBSET_IDS_SUM],
+                               (unsigned long long)ss[DFK_SUBSET_IDS_XOR], (unsigned long long)ss[DFK_SUBSET_EOI_SUM], (unsigned long long)ss[DFK_SUBSET_EOI_XOR]);
+                    }
                 }
             }
             t_g_write = tw_graph;

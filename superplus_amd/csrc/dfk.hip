@@ -2139,5 +2139,6 @@ int dfk_get_stats(dfk_ctx* c, dfk_stats* out)
 #include "dfk_graph.inc"
 #include "dfk_paths.inc"
 #include "dfk_hops.inc"
+#include "dfk_subset.inc"
 #include "dfk_paths_shard.inc"
 #include "dfk_pbf.inc"

@@ -39,7 +39,14 @@ struct HostGraph {
     struct PathState* paths = nullptr;                               // dfk_paths.inc
     struct PathState* hops_arrays = nullptr;                         // dfk_hops_build_arrays' result, nothing else in it (dfk_hops.inc)
     void (*paths_free)(struct PathState*) = nullptr;
-    ~HostGraph() { if (paths && paths_free) paths_free(paths); if (hops_arrays && paths_free) paths_free(hops_arrays); }
+    struct SubsetResult* subset_arrays = nullptr;                    // dfk_subset_build_arrays' result (dfk_subset.inc)
+    void (*subset_free)(struct SubsetResult*) = nullptr;
+    ~HostGraph()
+    {
+        if (paths && paths_free) paths_free(paths);
+        if (hops_arrays && paths_free) paths_free(hops_arrays);
+        if (subset_arrays && subset_free) subset_free(subset_arrays);
+    }
 };
 
 inline uint32_t base_at(const uint8_t* p, uint64_t i) { return (p[i >> 2] >> (2 * (i & 3))) & 3u; }

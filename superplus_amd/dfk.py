@@ -13,7 +13,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DFK_LIB") or os.path.join(_HERE, "libdfk.so")      # DFK_LIB: a developer's timing variant (tools/)
-ABI_VERSION = 2
+ABI_VERSION = 3
 F_KEEP_PRE_ADJ = 1
 F_KEEP_INPUTS = 2
 F_MARK_BADS = 4
@@ -32,6 +32,7 @@ EXPORTS = [
     "dfk_paths_var_bytes", "dfk_paths_write_part", "dfk_shard_pidx_pairs", "dfk_shard_pidx_write", "dfk_shard_dup_keys", "dfk_shard_dup_answer", "dfk_shard_dup_write",
     "dfk_bads_sums", "dfk_bads_write", "dfk_bads_write_part",
     "dfk_hops_build", "dfk_hops_build_bci", "dfk_hops_build_arrays", "dfk_hops_stats", "dfk_hops_fetch", "dfk_hops_write",
+    "dfk_subset_build", "dfk_subset_build_arrays", "dfk_subset_stats", "dfk_subset_fetch", "dfk_subset_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -42,6 +43,11 @@ CK = ["PATHS_SUM", "PATHS_XOR", "N_READS", "N_PLACED", "N_PATH_EDGES", "INV_SUM"
 # dfk_hops_stats' words (include/dfk.h, DFK_HOPS_*)
 HOPS_WORDS = 16
 HOPS = ["m1", "m2", "m3", "pairs", "searched", "extended", "host_edges", "most_rounds", "us", "us_index", "us_m12", "us_m3", "us_host", "largest_x", "ranges"]
+# dfk_subset_stats' words (include/dfk.h, DFK_SUBSET_*)
+SUBSET_WORDS = 16
+SUBSET = ["eoi", "ids", "path_entries", "index_entries", "ranges", "one_read_only", "us", "us_sweep", "us_gather", "us_index",
+          "ids_sum", "ids_xor", "eoi_sum", "eoi_xor"]
+SUBSET_FILES = ("a.sub.ids", "a.sub.eoi", "a.sub.paths", "a.sub.paths.inv")
 VERIFY = ["placed", "broken", "hits", "consistent", "no_anchor", "all_consistent", "dict_bad", "outside"]
 
 
@@ -340,6 +346,47 @@ class Dfk:
         n = C.c_uint64(); dg = (C.c_uint64 * 2)()
         _check(lib().dfk_hops_write(self._ctx, None if path is None else path.encode(), C.byref(n), dg))
         return n.value, (int(dg[0]), int(dg[1]))
+
+    def subset_build(self, pairs=None):
+        """dfk_subset_build: the subset of interest from the edge pairs (None = the context's own hops result; else int32[n, 2]);
+        returns subset_stats()."""
+        if pairs is None:
+            _check(lib().dfk_subset_build(self._ctx, None, C.c_uint64(0)))
+        else:
+            pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+            room = pairs if len(pairs) else np.zeros((1, 2), np.int32)      # (an empty list is still a list: NULL would mean the hops result)
+            _check(lib().dfk_subset_build(self._ctx, _p(room), C.c_uint64(len(pairs))))
+        return self.subset_stats()
+
+    def subset_build_arrays(self, inv, paths, pairs, reads_per_batch=0, directory=None):
+        """dfk_subset_build_arrays: the same stage on arrays (paths: a list of edge lists, one per read; pairs: [(e1, e2)]); with a
+        directory the four files a.sub.* are written there.  Returns subset_stats()."""
+        inv = np.ascontiguousarray(inv, np.int32)
+        first = np.zeros(len(paths) + 1, np.uint64)
+        first[1:] = np.cumsum([len(p) for p in paths], dtype=np.uint64)
+        edges = np.ascontiguousarray([e for p in paths for e in p] or [0], np.int32)
+        pr = np.ascontiguousarray(list(pairs) or [(0, 0)], np.int32).reshape(-1, 2)
+        _check(lib().dfk_subset_build_arrays(self._ctx, C.c_uint64(len(inv)), _p(inv), C.c_uint64(len(paths)), _p(first), _p(edges), _p(pr),
+                                             C.c_uint64(len(pairs)), C.c_uint64(reads_per_batch), None if directory is None else str(directory).encode()))
+        return self.subset_stats()
+
+    def subset_stats(self):
+        """dfk_subset_stats: {counter: value} -- eoi, ids, path and index entries, ranges, pairs taken through one read only, times, digests."""
+        out = (C.c_uint64 * SUBSET_WORDS)()
+        _check(lib().dfk_subset_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(SUBSET)}
+
+    def subset_fetch(self):
+        """dfk_subset_fetch: (read_ids, eoi), ascending uint64."""
+        ni, ne = C.c_uint64(), C.c_uint64()
+        _check(lib().dfk_subset_fetch(self._ctx, None, C.c_uint64(0), C.byref(ni), None, C.c_uint64(0), C.byref(ne)))
+        ids, eoi = np.zeros(ni.value, np.uint64), np.zeros(ne.value, np.uint64)
+        _check(lib().dfk_subset_fetch(self._ctx, _p(ids), C.c_uint64(ni.value), C.byref(ni), _p(eoi), C.c_uint64(ne.value), C.byref(ne)))
+        return ids, eoi
+
+    def subset_write(self, directory):
+        """dfk_subset_write: a.sub.ids, a.sub.eoi, a.sub.paths, a.sub.paths.inv into `directory` (which must exist)."""
+        _check(lib().dfk_subset_write(self._ctx, None if directory is None else str(directory).encode()))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
