@@ -206,6 +206,18 @@ int dfk_write_kvec_part(dfk_ctx* ctx, const char* path, int flags, uint64_t firs
 
 int dfk_get_stats(dfk_ctx* ctx, dfk_stats* out);
 
+/* The adjacency clean-up's set of boundary k-mers is allocated when the last pass's count is about to start, cut to
+ * the largest free block, and filled from the finished parts while that count runs.  What became of that set in the
+ * last run, and the slots of the set the clean-up used (0: it built none). */
+#define DFK_ADJ_NOT_APPLICABLE    0u   /* one pass, one stream (DFK_NO_OVERLAP), min_freq 1, a sharded run, or no finished part had a list */
+#define DFK_ADJ_USED              1u
+#define DFK_ADJ_DISCARDED_LOW     2u   /* the guess of the run's keys was too low: the set would be loaded past 0.6; rebuilt after the count */
+#define DFK_ADJ_DISCARDED_LIST    3u   /* a boundary list overflowed or the lists' totals disagree; rebuilt after the count */
+#define DFK_ADJ_NO_BLOCK          4u   /* no free block held a set at load <= 0.6 at that moment; built after the count */
+#define DFK_ADJ_DROPPED_FOR_ALLOC 5u   /* the last pass needed the room; built after the count */
+#define DFK_ADJ_SWITCHED_OFF      6u   /* DFK_NO_EARLY_SET=1 */
+int dfk_adj_outcome(dfk_ctx* ctx, uint32_t* outcome, uint64_t* slots);
+
 /* ---- the graph of the solid k-mers (single-GPU counts) ----
  * dfk_graph_build replaces, on the dictionary of the last dfk_count*:
  *   buildEdges         (paths/long/BuildReadQGraph48.cc:505-530, EdgeBuilder :320-503): the unipath edges, each once

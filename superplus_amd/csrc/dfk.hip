@@ -3,6 +3,7 @@
 #include "../../include/dfk.h"
 #include "dfk_kernels.h"
 #include "dfk_arena.h"
+#include "dfk_adj_plan.h"
 
 #include <algorithm>
 #include <chrono>
@@ -97,7 +98,13 @@ struct dfk_ctx {
     hipDeviceProp_t prop{};
     dfk::Arena arena{dev_get, dev_give};       // all device memory of a run (dfk_arena.h); the members below forward to it
     uint64_t &budget = arena.budget, &held = arena.held, &peak = arena.peak, &alloc_seq = arena.alloc_seq, &first_chunk_hint = arena.first_chunk_hint;
-    int alloc(DevBuf& b, size_t bytes, const char* what, Place where = Place::High) { return arena.alloc(b, bytes, what, where) ? fail(DFK_E_NOMEM, "%s", arena.err.c_str()) : 0; }
+    int alloc(DevBuf& b, size_t bytes, const char* what, Place where = Place::High)
+    {
+        int e = arena.alloc(b, bytes, what, where);
+        // the set made under the last pass's count (early set, below) never costs that pass anything: it goes first
+        if (e && (early_due || early_held)) { TRACE("no room for %s: the early boundary k-mer set goes", what); drop_early_set(dfk::ADJ_DROPPED_FOR_ALLOC); e = arena.alloc(b, bytes, what, where); }
+        return e ? fail(DFK_E_NOMEM, "%s", arena.err.c_str()) : 0;
+    }
     void release(DevBuf& b) { arena.release(b); }
     void shrink(DevBuf& b, size_t keep) { arena.shrink(b, keep); }
     void release_since(uint64_t mark, const DevBuf* keep = nullptr) { arena.release_since(mark, keep); }
@@ -138,7 +145,26 @@ struct dfk_ctx {
     void* sh_staged[6] = {};                  // dfk_shard_begin_host: this rank's inputs on the device (hipMalloc, outside the arena)
     uint64_t sh_b0 = 0, sh_b1 = 0, sh_q0 = 0, sh_q1 = 0, sh_staged_reads = 0;   //   the byte ranges of the whole set's arrays they hold, and how many reads
     DevBuf adj_keys, adj_src; uint64_t adj_n = 0;
-    DevBuf set; uint64_t set_mask = 0;
+    DevBuf set; uint64_t set_slots = 0;
+    // The early set: the boundary k-mer set allocated when the last pass's count is about to start, filled on the second
+    // stream (k_fill_u64, then the lists of the finished parts) while that count runs; stage_adjacency adds the last part
+    // and uses it, or discards it.  early_due: allocated, its kernels go behind the next k_count launch; early_held: they
+    // have been queued; early_parts: the parts whose lists they insert.  adj_outcome/adj_slots: dfk_adj_outcome.
+    bool early_due = false, early_held = false;
+    size_t early_parts = 0;
+    uint32_t adj_outcome = dfk::ADJ_NOT_APPLICABLE; uint64_t adj_slots = 0;
+    void drop_early_set(uint32_t why)                  // what runs on it ends first; then it is released and forgotten
+    {
+        if (!early_due && !early_held) return;
+        if (stream2) (void)hipStreamSynchronize(stream2);
+        release(set); set = DevBuf{}; set_slots = 0;
+        early_due = early_held = false; adj_outcome = why; adj_slots = 0;
+    }
+    void forget_early_set()                            // its block has gone back with a pass that was undone (release_since)
+    {
+        if (early_due || early_held) { set = DevBuf{}; set_slots = 0; adj_outcome = dfk::ADJ_NOT_APPLICABLE; adj_slots = 0; }
+        early_due = early_held = false;
+    }
     double t_upload_done = 0;                 // wall_now() when the last piece of the bases had arrived (run_under_upload)
     uint32_t shard_world = 1, shard_log2_nb = 0;
     void* shard_state = nullptr;              // bucket table + count state kept between the passes of a sharded run
@@ -172,6 +198,7 @@ struct dfk_ctx {
         shard_send_pass[0] = shard_send_pass[1] = ~0u;
         have = false; sorted_ok = sorted_pre_ok = false; sorted.clear(); sorted_pre.clear(); hist.clear();
         n_solid = 0; adj_n = 0; shard_open = false;
+        early_due = early_held = false; set_slots = 0;
         if (shard_state) { shard_state_free(shard_state); shard_state = nullptr; }
         for (void*& p : sh_staged) if (p) { (void)hipFree(p); p = nullptr; }
         budget += budget_taken; budget_taken = 0;
@@ -757,6 +784,26 @@ int launch_boundary_list(dfk_ctx* c)
     return 0;
 }
 
+// The early set's kernels, on the second stream behind the gate of the last pass's k_count: the fill, then the lists of
+// the finished parts.  The newest of those lists was queued on this stream just before (launch_boundary_list), the others
+// under earlier counts: stream order covers them all.  Nobody has read the lists' counters yet, so the kernel checks them.
+int launch_early_set(dfk_ctx* c)
+{
+    c->early_due = false;
+    if (!c->set.p) return 0;
+    hipLaunchKernelGGL(k_fill_u64, dim3(2048), dim3(256), 0, c->stream2, (uint64_t*)c->set.p, c->set_slots * 2, ~0ull);
+    for (size_t i = 0; i < c->early_parts; ++i) {
+        const dfk_ctx::Part& pt = c->parts[i];
+        if (!pt.n_blist) continue;
+        const unsigned long long* ctl = (const unsigned long long*)((const char*)pt.buf.p + pt.blist);
+        hipLaunchKernelGGL(k_set_insert_list, dim3((unsigned)((pt.n_blist + 255) / 256)), dim3(256), 0, c->stream2, (const uint4*)pt.buf.p,
+                           (const uint32_t*)(ctl + 2), pt.n_blist, (SetSlot*)c->set.p, c->set_slots, ctl);
+    }
+    c->early_held = true;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // one k_count launch over `n_items` device-resident items; overflowed items come back as bucket ranges
 template <int K, int NBC>
 int launch_count(dfk_ctx* c, const Partition& P, const ItemRange* d_items, uint64_t n_items, const CountRun& R,
@@ -781,13 +828,14 @@ int launch_count(dfk_ctx* c, const Partition& P, const ItemRange* d_items, uint6
                        (ItemRange*)d_ovf.p, d_sub, c->d_resident);
     HIP_TRY(hipGetLastError());
     c->resident_target += R.grid;
-    if (c->after_count_launch || c->pending_blist >= 0) {
+    if (c->after_count_launch || c->pending_blist >= 0 || c->early_due) {
         // what the second stream is about to run beside this launch waits until its persistent workgroups are all in place
         // (at most 2 ms: then it goes ahead and the gate says so)
         hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, c->stream2, (const unsigned int*)c->d_resident, c->resident_target, 200000ull, c->d_resident + 1);
     }
     if (c->after_count_launch) { std::function<int()> f; f.swap(c->after_count_launch); rc = f(); if (rc) return rc; }
     rc = launch_boundary_list(c); if (rc) return rc;
+    if (c->early_due) { rc = launch_early_set(c); if (rc) return rc; }
     *kernel_ms += tk.stop();
     CountGlobals g{};
     HIP_TRY(hipMemcpyAsync(&g, R.g, sizeof g, hipMemcpyDeviceToHost, c->stream));
@@ -1175,18 +1223,70 @@ int stage_count(dfk_ctx* c, const Partition& P, CountRun& R, bool have_bc)
 // ------------------------------------------------------------------ stage: adjacency (a6)
 // k_count has already settled every context bit whose neighbour was counted in the same table.  What is
 // left (pad byte 0 of an entry) concerns neighbours in other items: those k-mers go into an HBM set.
+static_assert(sizeof(SetSlot) == ADJ_SLOT_BYTES, "dfk_adj_plan.h sizes the set in SetSlots");
+
+// the set for `keys` keys, cut to what is free (dfk_adj_plan.h); not filled
+int alloc_set(dfk_ctx* c, uint64_t keys)
+{
+    const std::vector<Arena::Free> blocks = c->arena.allocatable_blocks();
+    const uint64_t room = c->budget > c->held ? c->budget - c->held : 0;
+    const uint64_t slots = adj_set_slots(keys, blocks, room);
+    if (!slots) {
+        if (g_trace) Arena::trace_free(blocks);
+        return fail(DFK_E_NOMEM, "no free block of device memory holds the boundary k-mer set (%llu keys: %.2f GB at load 0.6; %.2f GB free of %.2f GB)",
+                    (unsigned long long)keys, adj_min_slots(keys) * (double)ADJ_SLOT_BYTES / 1e9, room / 1e9, c->budget / 1e9);
+    }
+    int rc = c->alloc(c->set, slots * sizeof(SetSlot), "boundary k-mer set"); if (rc) return rc;
+    c->set_slots = slots; c->adj_slots = slots;
+    return 0;
+}
+
 int build_set(dfk_ctx* c)
 {
-    uint64_t slots = 1ull << std::max<uint32_t>(10, ceil_log2(2 * c->n_boundary + 2));
-    int rc = c->alloc(c->set, slots * sizeof(SetSlot), "boundary k-mer set"); if (rc) return rc;
-    c->set_mask = slots - 1;
-    hipLaunchKernelGGL(k_fill_u64, dim3(2048), dim3(256), 0, c->stream, (uint64_t*)c->set.p, slots * 2, ~0ull);
+    int rc = alloc_set(c, c->n_boundary); if (rc) return rc;
+    hipLaunchKernelGGL(k_fill_u64, dim3(2048), dim3(256), 0, c->stream, (uint64_t*)c->set.p, c->set_slots * 2, ~0ull);
     for (const dfk_ctx::Part& pt : c->parts)
         if (pt.n)
             hipLaunchKernelGGL(k_set_insert, dim3((unsigned)((pt.n + 255) / 256)), dim3(256), 0, c->stream,
-                               (const uint4*)pt.buf.p, pt.n, (SetSlot*)c->set.p, c->set_mask);
+                               (const uint4*)pt.buf.p, pt.n, (SetSlot*)c->set.p, c->set_slots);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// Called when the range about to be counted is the last one, [lo, sub_nb): the parts of [0, lo) are finished.  Guesses the
+// run's boundary keys from their lists, sizes the set to the largest free block and allocates it; launch_count then
+// queues its fill and the finished parts' lists behind k_count (launch_early_set).  Whatever stands in the way -- a
+// switch, no list, no block -- is the outcome dfk_adj_outcome reports, and the set is made after the count as before.
+// `reserve`: what the pass is known to ask for yet, whatever its data (the overflow list of its launch, the hole moves
+// of finish_part): the set leaves that much of the free room alone.  What a pass may need beyond that (the fallback of
+// hot buckets) it gets by taking the set's room back (dfk_ctx::alloc).
+void plan_early_set(dfk_ctx* c, uint32_t sub_nb, uint32_t lo, uint64_t reserve)
+{
+    c->adj_outcome = ADJ_NOT_APPLICABLE; c->adj_slots = 0;
+    if (!c->want_blist || c->cfg.min_freq <= 1 || !c->stream2 || getenv("DFK_NO_OVERLAP") || !lo) return;
+    std::vector<uint64_t> n_blist;
+    bool listed = true;
+    for (const dfk_ctx::Part& pt : c->parts) { n_blist.push_back(pt.n_blist); listed = listed && pt.listed; }
+    const double scale = getenv("DFK_EARLY_SET_SCALE") ? atof(getenv("DFK_EARLY_SET_SCALE")) : 1.0;
+    const uint64_t est = adj_estimate_keys(n_blist, sub_nb, lo, scale);
+    if (!listed || !est) return;                                       // (a part without its list: the set is built by streaming the parts)
+    if (getenv("DFK_NO_EARLY_SET")) { c->adj_outcome = ADJ_SWITCHED_OFF; return; }
+    const std::vector<Arena::Free> blocks = c->arena.allocatable_blocks();
+    const uint64_t free_now = c->budget > c->held ? c->budget - c->held : 0, room = free_now > reserve ? free_now - reserve : 0;
+    const uint64_t slots = adj_set_slots(est, blocks, room);
+    if (g_trace) {
+        TRACE("early set: estimate %llu keys from %zu parts (%u of %u buckets), %llu slots (%.2f GB, load %.3f), %.2f GB free (%.3f GB of it kept for the pass) in %zu blocks:",
+              (unsigned long long)est, n_blist.size(), lo, sub_nb, (unsigned long long)slots, slots * (double)ADJ_SLOT_BYTES / 1e9,
+              slots ? (double)est / (double)slots : 0.0, free_now / 1e9, reserve / 1e9, blocks.size());
+        Arena::trace_free(blocks);
+    }
+    c->adj_outcome = ADJ_NO_BLOCK;
+    if (!slots) return;
+    if (c->arena.alloc(c->set, slots * sizeof(SetSlot), "boundary k-mer set")) { c->set = DevBuf{}; return; }
+    c->set_slots = slots; c->adj_slots = slots;
+    c->early_parts = c->parts.size();
+    c->early_due = true;
+    c->adj_outcome = ADJ_USED;                                         // (until something else becomes of it)
 }
 
 // DFK_F_KEEP_PRE_ADJ: the kmers.kvec view (contexts before any clean-up)
@@ -1222,29 +1322,51 @@ int stage_adjacency(dfk_ctx* c)
             HIP_TRY(hipStreamSynchronize(c->stream2));
         }
         if (listed) {
+            // the lists' counters, all parts in one read-back
+            std::vector<unsigned long long> ctl(2 * c->parts.size(), 0);
+            for (size_t i = 0; i < c->parts.size(); ++i)
+                if (c->parts[i].blist) HIP_TRY(hipMemcpyAsync(&ctl[2 * i], (const char*)c->parts[i].buf.p + c->parts[i].blist, 16, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
             uint64_t total = 0;
-            for (const dfk_ctx::Part& pt : c->parts) {
+            for (size_t i = 0; i < c->parts.size(); ++i) {
+                const dfk_ctx::Part& pt = c->parts[i];
                 if (!pt.blist) continue;
-                unsigned long long ctl[2] = {0, 0};
-                HIP_TRY(hipMemcpy(ctl, (const char*)pt.buf.p + pt.blist, 16, hipMemcpyDeviceToHost));
-                if (ctl[1] || ctl[0] != pt.n_blist)
-                    return fail(DFK_E_HIP, "boundary list: %llu entries listed, the count kernels reported %llu", ctl[0], (unsigned long long)pt.n_blist);
+                if (ctl[2 * i + 1] || ctl[2 * i] != pt.n_blist) {
+                    c->drop_early_set(ADJ_DISCARDED_LIST);
+                    return fail(DFK_E_HIP, "boundary list: %llu entries listed, the count kernels reported %llu", ctl[2 * i], (unsigned long long)pt.n_blist);
+                }
                 total += pt.n_blist;
             }
             // (parts without unresolved bits have no list; the total must be the run's)
             if (total != c->n_boundary) listed = false;
         }
+        // the set started under the last count (plan_early_set) holds the lists of the first early_parts parts: it serves
+        // if the lists are good and the run's keys, now known, still load it to 0.6 at most
+        if (c->early_held) {
+            if (!listed) c->drop_early_set(ADJ_DISCARDED_LIST);
+            else if (!adj_load_ok(c->n_boundary, c->set_slots)) {
+                TRACE("early set: %llu keys in %llu slots would be load %.3f: discarded", (unsigned long long)c->n_boundary, (unsigned long long)c->set_slots, (double)c->n_boundary / (double)c->set_slots);
+                c->drop_early_set(ADJ_DISCARDED_LOW);
+            }
+        }
+        const bool early = c->early_held;
+        c->early_held = false;                                         // from here on it is the set, released below like any other
         if (!listed) { rc = build_set(c); if (rc) return rc; }
         else {
-            uint64_t slots = 1ull << std::max<uint32_t>(10, ceil_log2(2 * c->n_boundary + 2));
-            rc = c->alloc(c->set, slots * sizeof(SetSlot), "boundary k-mer set"); if (rc) return rc;
-            c->set_mask = slots - 1;
-            hipLaunchKernelGGL(k_fill_u64, dim3(2048), dim3(256), 0, c->stream, (uint64_t*)c->set.p, slots * 2, ~0ull);
-            for (const dfk_ctx::Part& pt : c->parts)
+            if (!early) {
+                rc = alloc_set(c, c->n_boundary); if (rc) return rc;
+                hipLaunchKernelGGL(k_fill_u64, dim3(2048), dim3(256), 0, c->stream, (uint64_t*)c->set.p, c->set_slots * 2, ~0ull);
+            }
+            for (size_t i = early ? c->early_parts : 0; i < c->parts.size(); ++i) {
+                const dfk_ctx::Part& pt = c->parts[i];
                 if (pt.n_blist)
                     hipLaunchKernelGGL(k_set_insert_list, dim3((unsigned)((pt.n_blist + 255) / 256)), dim3(256), 0, c->stream, (const uint4*)pt.buf.p,
-                                       (const uint32_t*)((const char*)pt.buf.p + pt.blist + 16), pt.n_blist, (SetSlot*)c->set.p, c->set_mask);
+                                       (const uint32_t*)((const char*)pt.buf.p + pt.blist + 16), pt.n_blist, (SetSlot*)c->set.p, c->set_slots,
+                                       (const unsigned long long*)nullptr);
+            }
             HIP_TRY(hipGetLastError());
+            TRACE("boundary k-mer set: %llu keys in %llu slots (load %.3f)%s", (unsigned long long)c->n_boundary, (unsigned long long)c->set_slots,
+                  (double)c->n_boundary / (double)c->set_slots, early ? ", filled under the last count but for the last part" : "");
         }
         DevBuf d_n; rc = c->alloc(d_n, 16, "probe counter"); if (rc) return rc;
         HIP_TRY(hipMemsetAsync(d_n.p, 0, 16, c->stream));
@@ -1254,10 +1376,10 @@ int stage_adjacency(dfk_ctx* c)
                 if (pt.n_blist)
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_adjacency_list<K>), dim3((unsigned)std::min<uint64_t>((pt.n_blist + 255) / 256, 16384)), dim3(256), 0,
                                        c->stream, (uint4*)pt.buf.p, (const uint32_t*)((const char*)pt.buf.p + pt.blist + 16), pt.n_blist,
-                                       (const SetSlot*)c->set.p, c->set_mask, (unsigned long long*)d_n.p);
+                                       (const SetSlot*)c->set.p, c->set_slots, (unsigned long long*)d_n.p);
             } else
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_adjacency<K>), dim3((unsigned)std::min<uint64_t>((pt.n + 255) / 256, 8192)), dim3(256), 0,
-                                   c->stream, (uint4*)pt.buf.p, pt.n, (const SetSlot*)c->set.p, c->set_mask, (unsigned long long*)d_n.p);
+                                   c->stream, (uint4*)pt.buf.p, pt.n, (const SetSlot*)c->set.p, c->set_slots, (unsigned long long*)d_n.p);
         }
         HIP_TRY(hipGetLastError());
         uint64_t np = 0;
@@ -1266,6 +1388,7 @@ int stage_adjacency(dfk_ctx* c)
         c->st.adj_probes = np;
         c->release(d_n); c->release(c->set);
     }
+    if (c->early_held) c->drop_early_set(ADJ_NOT_APPLICABLE);          // (nothing to clean up after all: no boundary entry in the whole run)
     c->st.ms_adjacency = t.stop();
     TRACE("adjacency done");
     return 0;
@@ -1320,6 +1443,7 @@ int run_typed(dfk_ctx* c, const Inputs& in, Prescan* pre = nullptr)
     CountRun R;
     rc = count_run_begin(c, &R); if (rc) return rc;
     c->want_blist = true; c->pending_blist = -1;
+    c->adj_outcome = ADJ_NOT_APPLICABLE; c->adj_slots = 0;
     // Passes over contiguous ranges of the fine buckets, each as large as the free HBM allows.  While a pass is
     // counted (LDS- and issue-bound) the next range is scattered on a second, low-priority stream (bound by
     // scattered atomics and stores): the two kernels share the CUs.  A pass that runs out of room (its estimate
@@ -1389,7 +1513,10 @@ int run_typed(dfk_ctx* c, const Inputs& in, Prescan* pre = nullptr)
                 if (r2 && r2 != DFK_E_NOMEM) return r2;                // NOMEM: this range is scattered after the count instead
             }
         }
+        // the last range: the boundary k-mer set is made now and filled from the finished parts while this range is counted
+        if (!rc && nlo == sub_nb && overlap) plan_early_set(c, sub_nb, lo, cur.sj.P.n_items * sizeof(ItemRange) + 16ull * R.grid * out_chunk<K>() + 4096);
         if (!rc) rc = count_run_nbc<K>(c, cur.sj.P, R, barcode_words(c, in.bc != nullptr));
+        if (c->early_due) c->drop_early_set(ADJ_NOT_APPLICABLE);       // (no k_count was launched)
         if (c->after_count_launch) {                                     // (no k_count was launched: an error on the way there)
             std::function<int()> f; f.swap(c->after_count_launch);
             if (!rc) { const int r3 = f(); if (r3) return r3; } else nxt.valid = false;
@@ -1397,6 +1524,7 @@ int run_typed(dfk_ctx* c, const Inputs& in, Prescan* pre = nullptr)
         if (rc == DFK_E_NOMEM || rc == E_SEGMENT_FULL) {
             HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipStreamSynchronize(c->stream2));
             c->release_since(cur.mark);                               // this pass and the one started under it
+            c->forget_early_set();                                   //   ... and the early set, if this was the last range (the redo may start it again)
             R.d_wg = R.big = R.d_part = DevBuf{};
             drop_events(cur); drop_events(nxt); nxt.valid = false;
             int rc2 = count_snapshot(c, &R, true); if (rc2) return rc2;
@@ -2130,6 +2258,13 @@ int dfk_get_stats(dfk_ctx* c, dfk_stats* out)
     }
     c->st.reserved[5] = c->held;                                             // device bytes the context holds right now
     *out = c->st;
+    return 0;
+}
+
+int dfk_adj_outcome(dfk_ctx* c, uint32_t* outcome, uint64_t* slots)
+{
+    if (!c || !outcome || !slots) return fail(DFK_E_ARG, "null argument");
+    *outcome = c->adj_outcome; *slots = c->adj_slots;
     return 0;
 }
 

@@ -98,6 +98,16 @@ public:
         for (const Chunk& k : chunks) for (const Free& f : k.free_list) best = std::max<uint64_t>(best, f.bytes);
         return std::min<uint64_t>(best, budget > held ? budget - held : 0);
     }
+    // every block alloc() could carve from now: the chunks' free blocks and, within the budget, a new chunk (offsets are
+    // within each block's own chunk; a new chunk's is 0)
+    std::vector<Free> allocatable_blocks() const
+    {
+        std::vector<Free> all;
+        for (const Chunk& k : chunks) all.insert(all.end(), k.free_list.begin(), k.free_list.end());
+        const uint64_t grow = budget > reserved ? (budget - reserved) & ~(uint64_t)0xFFF : 0;
+        if (grow) all.push_back(Free{0, grow});
+        return all;
+    }
     void release(DevBuf& b)
     {
         if (!b.p) return;

@@ -2027,31 +2027,35 @@ __device__ __forceinline__ uint64_t set_hash(uint64_t w0, uint64_t w1)
     h ^= h >> 29;
     return h;
 }
+// The set takes any number of slots (the host cuts it to the free block it lives in, dfk_adj_plan.h): a key's home is
+// the high product of its hash and the slot count, a probe steps by one and wraps there.
+__device__ __forceinline__ uint64_t set_home(uint64_t w0, uint64_t w1, uint64_t slots) { return __umul64hi(set_hash(w0, w1), slots); }
+__device__ __forceinline__ uint64_t set_next(uint64_t s, uint64_t slots) { return s + 1 == slots ? 0 : s + 1; }
 
 __global__ void __launch_bounds__(256)
-k_set_insert(const uint4* __restrict__ entries, uint64_t n, SetSlot* __restrict__ set, uint64_t mask)
+k_set_insert(const uint4* __restrict__ entries, uint64_t n, SetSlot* __restrict__ set, uint64_t slots)
 {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (!(entries[2 * i + 1].w & 0xFFu)) return;                     // only k-mers with unresolved context bits can be asked for
     uint4 a = entries[2 * i];
     uint64_t w0 = (uint64_t)a.x | ((uint64_t)a.y << 32), w1 = (uint64_t)a.z | ((uint64_t)a.w << 32);
-    uint64_t s = set_hash(w0, w1) & mask;
+    uint64_t s = set_home(w0, w1, slots);
     for (;;) {
         unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&set[s].w0), ~0ull, (unsigned long long)w0);
         if (old == ~0ull) { set[s].w1 = w1; return; }
-        s = (s + 1) & mask;
+        s = set_next(s, slots);
     }
 }
 
-__device__ __forceinline__ bool set_has(const SetSlot* __restrict__ set, uint64_t mask, uint64_t w0, uint64_t w1)
+__device__ __forceinline__ bool set_has(const SetSlot* __restrict__ set, uint64_t slots, uint64_t w0, uint64_t w1)
 {
-    uint64_t s = set_hash(w0, w1) & mask;
+    uint64_t s = set_home(w0, w1, slots);
     for (;;) {
         SetSlot v = set[s];
         if (v.w0 == ~0ull) return false;
         if (v.w0 == w0 && v.w1 == w1) return true;
-        s = (s + 1) & mask;
+        s = set_next(s, slots);
     }
 }
 
@@ -2093,18 +2097,23 @@ k_boundary_list(const uint4* __restrict__ entries, uint64_t n, uint32_t* __restr
     }
 }
 
+// `ctl` != null: the host has not read the list's counters yet (the set is being made under the last pass's count).  A
+// list that is not exactly the n entries expected may hold anything behind what was written: it is left alone, and
+// the host, which checks the same counters before it uses the set, discards the set.
 __global__ void __launch_bounds__(256)
-k_set_insert_list(const uint4* __restrict__ entries, const uint32_t* __restrict__ list, uint64_t n, SetSlot* __restrict__ set, uint64_t mask)
+k_set_insert_list(const uint4* __restrict__ entries, const uint32_t* __restrict__ list, uint64_t n, SetSlot* __restrict__ set, uint64_t slots,
+                  const unsigned long long* __restrict__ ctl)
 {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
+    if (ctl && (ctl[0] != n || ctl[1])) return;
     const uint4 a = entries[2 * (uint64_t)list[t]];
     const uint64_t w0 = (uint64_t)a.x | ((uint64_t)a.y << 32), w1 = (uint64_t)a.z | ((uint64_t)a.w << 32);
-    uint64_t s = set_hash(w0, w1) & mask;
-    for (uint64_t step = 0; step <= mask; ++step) {                      // (the host sizes the set at load <= 0.6; a full one must still let every wave end)
+    uint64_t s = set_home(w0, w1, slots);
+    for (uint64_t step = 0; step < slots; ++step) {                      // (the host sizes the set at load <= 0.6; a full one must still let every wave end)
         unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&set[s].w0), ~0ull, (unsigned long long)w0);
         if (old == ~0ull) { set[s].w1 = w1; return; }
-        s = (s + 1) & mask;
+        s = set_next(s, slots);
     }
 }
 
@@ -2126,7 +2135,7 @@ __device__ __forceinline__ void canon_words(u128 F, uint64_t* w0, uint64_t* w1)
 // the set holds exactly the solid k-mers that have such bits (adjacency is mutual: if X's neighbour Y was
 // counted in another item, then Y's neighbour X was too).  Returns the number of look-ups.
 template <int K>
-__device__ __forceinline__ uint32_t adjacency_entry(uint4* __restrict__ entries, uint64_t i, const SetSlot* __restrict__ set, uint64_t mask)
+__device__ __forceinline__ uint32_t adjacency_entry(uint4* __restrict__ entries, uint64_t i, const SetSlot* __restrict__ set, uint64_t slots)
 {
     const u128 m = KTraits<K>::mask();
     uint4 b = entries[2 * i + 1];
@@ -2146,7 +2155,7 @@ __device__ __forceinline__ uint32_t adjacency_entry(uint4* __restrict__ entries,
         }
         uint64_t w0, w1; canon_words<K>(v, &w0, &w1);
         ++probes;
-        if (!set_has(set, mask, w0, w1)) ctx &= ~(1u << bit);
+        if (!set_has(set, slots, w0, w1)) ctx &= ~(1u << bit);
     }
     b.y = (b.y & 0xFFFFFFu) | (ctx << 24);
     b.w = 0;
@@ -2166,24 +2175,24 @@ __device__ __forceinline__ void add_probes(unsigned long long probes, unsigned l
 
 template <int K>
 __global__ void __launch_bounds__(256)
-k_adjacency(uint4* __restrict__ entries, uint64_t n, const SetSlot* __restrict__ set, uint64_t mask,
+k_adjacency(uint4* __restrict__ entries, uint64_t n, const SetSlot* __restrict__ set, uint64_t slots,
             unsigned long long* __restrict__ n_probes)
 {
     unsigned long long probes = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        probes += adjacency_entry<K>(entries, i, set, mask);
+        probes += adjacency_entry<K>(entries, i, set, slots);
     add_probes(probes, n_probes);
 }
 
 // the same over a part's boundary list (k_boundary_list): every lane has an entry to settle
 template <int K>
 __global__ void __launch_bounds__(256)
-k_adjacency_list(uint4* __restrict__ entries, const uint32_t* __restrict__ list, uint64_t n, const SetSlot* __restrict__ set, uint64_t mask,
+k_adjacency_list(uint4* __restrict__ entries, const uint32_t* __restrict__ list, uint64_t n, const SetSlot* __restrict__ set, uint64_t slots,
                  unsigned long long* __restrict__ n_probes)
 {
     unsigned long long probes = 0;
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.x * blockDim.x)
-        probes += adjacency_entry<K>(entries, (uint64_t)list[t], set, mask);
+        probes += adjacency_entry<K>(entries, (uint64_t)list[t], set, slots);
     add_probes(probes, n_probes);
 }
 
@@ -2434,13 +2443,13 @@ k_adj_place(const uint64_t* __restrict__ list, const SetSlot* __restrict__ tmp_k
 }
 
 __global__ void __launch_bounds__(256)
-k_adj_answer(const SetSlot* __restrict__ keys, uint64_t n, const SetSlot* __restrict__ set, uint64_t mask,
+k_adj_answer(const SetSlot* __restrict__ keys, uint64_t n, const SetSlot* __restrict__ set, uint64_t slots,
              uint8_t* __restrict__ present)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     SetSlot k = keys[i];
-    present[i] = set_has(set, mask, k.w0, k.w1) ? 1 : 0;
+    present[i] = set_has(set, slots, k.w0, k.w1) ? 1 : 0;
 }
 
 __global__ void __launch_bounds__(256)

@@ -534,7 +534,7 @@ int dfk_shard_adj_answer(dfk_ctx* c, const void* d_keys, uint64_t n_keys, void* 
     HIP_TRY(hipSetDevice(c->device));
     CallClock clock(c, &c->st.ms_adjacency);
     hipLaunchKernelGGL(k_adj_answer, dim3((unsigned)((n_keys + 255) / 256)), dim3(256), 0, c->stream, (const SetSlot*)d_keys, n_keys,
-                       (const SetSlot*)c->set.p, c->set_mask, (uint8_t*)d_present);
+                       (const SetSlot*)c->set.p, c->set_slots, (uint8_t*)d_present);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;

@@ -24,7 +24,7 @@ ENTRY_DTYPE = np.dtype([("w0", "<u8"), ("w1", "<u8"), ("edge_id", "<u4"), ("coun
 EXPORTS = [
     "dfk_create", "dfk_destroy", "dfk_last_error", "dfk_abi_version", "dfk_count", "dfk_count_bci", "dfk_count_device",
     "dfk_hint_file_range", "dfk_qual_hist", "dfk_paths_sink", "dfk_good_lens", "dfk_spectrum", "dfk_spectrum_json", "dfk_solid_count", "dfk_solid_fetch", "dfk_solid_fetch_unsorted", "dfk_solid_digest",
-    "dfk_write_kvec", "dfk_write_kvec_part", "dfk_get_stats", "dfk_shard_begin", "dfk_shard_begin_host", "dfk_shard_plan", "dfk_shard_partition", "dfk_shard_partition_begin", "dfk_shard_partition_end", "dfk_shard_recv_buffer", "dfk_shard_count", "dfk_shard_adj_queries",
+    "dfk_write_kvec", "dfk_write_kvec_part", "dfk_get_stats", "dfk_adj_outcome", "dfk_shard_begin", "dfk_shard_begin_host", "dfk_shard_plan", "dfk_shard_partition", "dfk_shard_partition_begin", "dfk_shard_partition_end", "dfk_shard_recv_buffer", "dfk_shard_count", "dfk_shard_adj_queries",
     "dfk_shard_adj_answer", "dfk_shard_adj_apply", "dfk_graph_build", "dfk_graph_stats", "dfk_graph_write",
     "dfk_shard_dict_share", "dfk_shard_dict_adopt", "dfk_shard_dict_whole",
     "dfk_paths_build", "dfk_paths_build_device", "dfk_paths_stats", "dfk_paths_write", "dfk_paths_fetch", "dfk_paths_index_write", "dfk_dups_write", "dfk_paths_index_dups_write",
@@ -48,6 +48,9 @@ SUBSET_WORDS = 16
 SUBSET = ["eoi", "ids", "path_entries", "index_entries", "ranges", "one_read_only", "us", "us_sweep", "us_gather", "us_index",
           "ids_sum", "ids_xor", "eoi_sum", "eoi_xor"]
 SUBSET_FILES = ("a.sub.ids", "a.sub.eoi", "a.sub.paths", "a.sub.paths.inv")
+# dfk_adj_outcome's codes (include/dfk.h, DFK_ADJ_*)
+ADJ_OUTCOMES = ["not applicable", "used", "discarded: guess too low", "discarded: list problem", "no block", "dropped for an allocation",
+                "switched off"]
 VERIFY = ["placed", "broken", "hits", "consistent", "no_anchor", "all_consistent", "dict_bad", "outside"]
 
 
@@ -420,6 +423,13 @@ class Dfk:
         s = Stats()
         _check(lib().dfk_get_stats(self._ctx, C.byref(s)))
         return s.asdict()
+
+    def adj_outcome(self):
+        """dfk_adj_outcome: (what became of the boundary k-mer set started under the last pass's count -- one of
+        ADJ_OUTCOMES -- , slots of the set the adjacency clean-up used)."""
+        code, slots = C.c_uint32(), C.c_uint64()
+        _check(lib().dfk_adj_outcome(self._ctx, C.byref(code), C.byref(slots)))
+        return ADJ_OUTCOMES[code.value], int(slots.value)
 
 
 def _mix(x):
