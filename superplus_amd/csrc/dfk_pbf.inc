@@ -101,7 +101,9 @@ int pbf_run(dfk_ctx* c, const dfk_pbf_input* in, dfk_pbf* R)
         std::vector<Batch> batches;
         const uint64_t per_read = 8ull * std::max(max_len[0], max_len[1]) + 4 + 32;
         const uint64_t room = std::max<uint64_t>(64ull << 20, c->largest_allocatable() / 4);
-        const uint64_t per_batch = std::max<uint64_t>(1, std::min<uint64_t>(n_reads, room / per_read));
+        uint64_t per_batch = std::max<uint64_t>(1, std::min<uint64_t>(n_reads, room / per_read));
+        if (const char* e = getenv("DFK_PBF_BATCH_READS")) per_batch = std::min(per_batch, std::max<uint64_t>(1, (uint64_t)atoll(e)));      // (tests: more than one batch)
+        const bool plan_in_lds = std::max(max_len[0], max_len[1]) <= PBF_LDS_LEN;
         for (uint64_t k0 = 0; k0 < n_reads; k0 += per_batch) {
             Batch B; B.k0 = k0; B.nk = std::min(per_batch, n_reads - k0);
             DevBuf ssz;
@@ -114,7 +116,9 @@ int pbf_run(dfk_ctx* c, const dfk_pbf_input* in, dfk_pbf* R)
             HIP_TRY(hipStreamSynchronize(c->stream));
             c->release(ssz);
             if ((rc = c->alloc(B.scratch, std::max<uint64_t>(1, words) * 4, "encoder scratch", Place::Low))) return rc;
-            if (std::max(max_len[0], max_len[1]) <= PBF_LDS_LEN)
+            TRACE("pbf: encoder batch of %llu reads from read %llu of %llu, %llu words of scratch, plan in %s", (unsigned long long)B.nk, (unsigned long long)B.k0,
+                  (unsigned long long)n_reads, (unsigned long long)words, plan_in_lds ? "LDS" : "HBM");
+            if (plan_in_lds)
                 hipLaunchKernelGGL(k_pbf_pq_plan_lds, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((B.nk + 63) / 64, 64ull * cus))), dim3(64), 0, c->stream, F, order, B.k0, B.nk,
                                    (const uint64_t*)B.soff.p, (uint32_t*)B.scratch.p, (uint32_t*)B.nblk.p, (uint64_t*)pq_sz.p + B.k0, bad);
             else

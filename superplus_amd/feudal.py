@@ -141,3 +141,26 @@ def pq_encode(q):
         i = j
     out.append(0)
     return bytes(out)
+
+
+def pq_blocks(buf):
+    """The blocks of one PQVec stream (feudal/PQVec.cc:87-127): [(n, bits, minq, values)] up to the terminating 0."""
+    buf = bytes(buf)
+    out = []
+    i = 0
+    while buf[i]:
+        n = buf[i]
+        nbits = buf[i + 1] & 7
+        size = (n * nbits + 17 + 7) >> 3
+        acc = int.from_bytes(buf[i + 1 : i + size], "little")
+        minq = (acc >> 3) & 63
+        out.append((n, nbits, minq, [minq + ((acc >> (9 + x * nbits)) & ((1 << nbits) - 1)) for x in range(n)]))
+        i += size
+    if i != len(buf) - 1:
+        raise ValueError("bytes behind the end of a PQVec stream")
+    return out
+
+
+def pq_decode(buf):
+    """The qualities one PQVec stream holds."""
+    return [v for b in pq_blocks(buf) for v in b[3]]

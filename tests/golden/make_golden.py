@@ -437,25 +437,30 @@ PBF_REF_CASES = [(2000, 11, 40, True, ("NUM_BUCKETS=5",)), (1500, 12, 300, False
                  (1200, 14, 25, True, ("NUM_BUCKETS=2",)), (1500, 15, 30, False, ("NUM_BUCKETS=7", "READS_PER_BC=90"))] + \
                 [(3000, 41, 40, True, extra) for extra in (("NUM_BUCKETS=8",), ("NUM_BUCKETS=16",), ("NUM_BUCKETS=9", "READS_PER_BC=400"),
                                                            ("NUM_BUCKETS=64",))]
+# and the edge profiles of tests/fastq_synth.py::make_fastq_edges: (profile, seed, arguments)
+PBF_EDGE_CASES = [("lds_edge", 61, ("NUM_BUCKETS=3",)), ("long", 62, ("NUM_BUCKETS=3",)), ("long_one_file", 63, ("NUM_BUCKETS=3",)),
+                  ("long", 62, ("NUM_BUCKETS=3", "READS_PER_BC=170"))]
 
 
 def pbf_ref():
     """tests/golden/pbf_ref.json: what the reference's own ParseBarcodedFastqs (single-threaded, see oracle/build_ref.sh)
-    writes for each of PBF_REF_CASES, as SHA-256 of the three files, with the SHA-256 of the input they were written from."""
+    writes for each of PBF_REF_CASES and PBF_EDGE_CASES, as SHA-256 of the three files, with the SHA-256 of the input they were written from."""
     import hashlib
     import json
     import tempfile
-    from tests.fastq_synth import case_name, fastq_digest, make_fastq
+    from tests.fastq_synth import case_name, edge_case_name, fastq_digest, make_fastq, make_fastq_edges
     binary = os.path.join(ROOT, "oracle", "_ref", "ParseBarcodedFastqs")
     if not os.path.exists(binary):
         raise SystemExit("oracle/_ref/ParseBarcodedFastqs missing: run oracle/build_ref.sh in the build container")
     out = {}
     with tempfile.TemporaryDirectory() as d:
-        for pairs, seed, n_bc, ragged, extra in PBF_REF_CASES:
-            make_fastq(d + "/a_1.fq.gz", d + "/a_2.fq.gz", pairs, seed, n_bc=n_bc, ragged=ragged)
+        cases = [(case_name(*c), lambda a, b, c=c: make_fastq(a, b, c[0], c[1], n_bc=c[2], ragged=c[3]), c[4]) for c in PBF_REF_CASES] + \
+                [(edge_case_name(*c), lambda a, b, c=c: make_fastq_edges(a, b, c[1], c[0]), c[2]) for c in PBF_EDGE_CASES]
+        for key, make, extra in cases:
+            make(d + "/a_1.fq.gz", d + "/a_2.fq.gz")
             subprocess.check_call([binary, "FASTQS={" + d + "/a_1.fq.gz," + d + "/a_2.fq.gz}", "OUT_HEAD=" + d + "/o/reads", "NUM_THREADS=1", *extra],
                                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-            e = out[case_name(pairs, seed, n_bc, ragged, extra)] = {"input": fastq_digest(d + "/a_1.fq.gz", d + "/a_2.fq.gz")}
+            e = out[key] = {"input": fastq_digest(d + "/a_1.fq.gz", d + "/a_2.fq.gz")}
             for ext in ("fastb", "qualp", "bci"):
                 e[ext] = hashlib.sha256(open(f"{d}/o/reads.{ext}", "rb").read()).hexdigest()
             subprocess.check_call(["rm", "-rf", d + "/o"])
