@@ -456,6 +456,18 @@ int dfk_paths_verify(dfk_ctx* ctx, const uint8_t* packed_bases, const uint64_t* 
               uint64_t* out /* [8] */);
 int dfk_paths_verify_device(dfk_ctx* ctx, const void* d_packed_bases, uint64_t packed_bytes, const void* d_base_off, const void* d_read_len,
               uint64_t n_reads, uint64_t* out /* [8] */);
+/* dfk_paths_verify_arrays  the verifier on paths given as host arrays, for tests that choose (and damage) their paths: the same
+ *                   kernel on the context's graph, k-mer index and tables, over `n_reads` reads of any number and their paths --
+ *                   offsets[i], and first[i] .. first[i + 1] of `edges` -- laid out as the pather leaves its batches and cut into
+ *                   batches of reads_per_batch (0 = one batch).  out[0..7] the eight counters, out[8..9] DFK_CK_PATHS_SUM / _XOR of
+ *                   the paths given.  Needs what dfk_paths_verify needs; leaves the context's paths, marks and results alone and
+ *                   holds no more of the device afterwards.  Refused before anything is launched (DFK_E_ARG): a null argument,
+ *                   first[0] != 0, a falling first, n_reads or first[n_reads] >= 2^31, a batch of 2^32 bytes or more (8 a read, 4
+ *                   an edge); DFK_E_INPUT: the reads' offset table, as dfk_paths_verify.  Edge ids and offsets of ANY value are
+ *                   let through: they are what the kernel is there to count. */
+int dfk_paths_verify_arrays(dfk_ctx* ctx, const uint8_t* packed_bases, const uint64_t* base_off, const uint32_t* read_len, uint64_t n_reads,
+              const int32_t* offsets /* [n_reads] */, const uint64_t* first /* [n_reads + 1] */, const int32_t* edges,
+              uint64_t reads_per_batch, uint64_t* out /* [10] */);
 
 /* ---- the data-parallel half of ParseBarcodedFastqs (10X/ParseBarcodedFastqs.cc:306-539) ----
  * The host inflates the two .gz files, cuts them into lines and decides where every barcode stands in the output (the buckets

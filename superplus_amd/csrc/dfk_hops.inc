@@ -357,12 +357,8 @@ int dfk_hops_build_arrays(dfk_ctx* c, uint64_t n_edges, uint64_t n_vertices, con
         int rc;
         for (uint64_t r0 = 0; r0 < N; r0 += per) {
             PathBatch B; B.r0 = r0; B.n = std::min(per, N - r0); B.file_base = 24 + 8 * r0 + 4 * first[r0];
-            std::vector<uint32_t> var, off(B.n);
-            for (uint64_t i = 0; i < B.n; ++i) {
-                off[i] = (uint32_t)(var.size() * 4);
-                var.push_back(0u); var.push_back(0u);
-                for (uint64_t k = first[r0 + i]; k < first[r0 + i + 1]; ++k) var.push_back((uint32_t)edges[k]);
-            }
+            std::vector<uint32_t> var, off;
+            layout_batch(first, edges, nullptr, r0, B.n, var, off);
             B.var_bytes = var.size() * 4;
             if (B.var_bytes >= (1ull << 32)) return fail(DFK_E_ARG, "a batch of %llu reads holds %llu bytes of paths: its offsets keep 32 bits", (unsigned long long)B.n, (unsigned long long)B.var_bytes);
             if ((rc = upload_vec(c, B.var, var, "a.paths data")) || (rc = upload_vec(c, B.elem_off, off, "a.paths offsets"))) return rc;

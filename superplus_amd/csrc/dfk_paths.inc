@@ -67,6 +67,20 @@ template <class T> int upload_vec(dfk_ctx* c, DevBuf& d, const std::vector<T>& v
     return 0;
 }
 
+// Reads [r0, r0 + n) of paths given as host arrays (first[i] .. first[i + 1] of `edges` are read i's), laid out as k_path_emit
+// leaves a batch: the offset word (offsets null: 0), a zero lastSkip word, then the edges; elem_off in bytes; an unplaced read is its
+// two words alone.  What the entries that take arrays upload (dfk_hops_build_arrays, dfk_subset_build_arrays, dfk_paths_verify_arrays).
+inline void layout_batch(const uint64_t* first, const int32_t* edges, const int32_t* offsets, uint64_t r0, uint64_t n,
+                         std::vector<uint32_t>& var, std::vector<uint32_t>& off)
+{
+    var.clear(); off.resize(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        off[i] = (uint32_t)(var.size() * 4);
+        var.push_back(offsets ? (uint32_t)offsets[r0 + i] : 0u); var.push_back(0u);
+        for (uint64_t k = first[r0 + i]; k < first[r0 + i + 1]; ++k) var.push_back((uint32_t)edges[k]);
+    }
+}
+
 // fwdEdgeXlat / revEdgeXlat, ToLeft / ToRight and digraphE's adjacency (in its own sorted order: the extension rules take
 // the first of equally good edges) as flat arrays
 int paths_tables(dfk_ctx* c, HostGraph* G, PathState* P)
@@ -777,8 +791,9 @@ int dups_write(dfk_ctx* c, PathState* P, const std::string& path, uint64_t* n_ma
 void release_path_lookup(dfk_ctx* c, HostGraph* G) { c->release(G->d_index); c->release(G->d_filter); G->d_index = G->d_filter = DevBuf{}; G->filter_words = 0; }
 
 // dfk_paths_verify: k_path_verify over every batch of the paths the context holds, against the reads given
+// (dfk_paths_verify_arrays: over the batches it laid out, and their digest as paths_build_typed takes the context's own)
 template <int K>
-int paths_verify_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in, uint64_t* out)
+int paths_verify_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in, const std::vector<PathBatch>& batches, uint64_t* out, uint64_t* digest)
 {
     DevBuf ctr; int rc = c->alloc(ctr, 8 * PV_N + 8, "verify counters", Place::Low); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(ctr.p, 0, 8 * PV_N + 8, c->stream));
@@ -792,7 +807,7 @@ int paths_verify_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in,
     HIP_TRY(hipMemcpyAsync(&bad, (char*)ctr.p + 8 * PV_N, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (bad) { c->release(ctr); return fail(DFK_E_INPUT, "verify: the reads' offset table is not monotone, runs past its array, or leaves a read fewer bytes than its bases need"); }
-    for (const PathBatch& b : P->batches)
+    for (const PathBatch& b : batches)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_verify<K>), dim3(grid_256(b.n, cus, 64)), dim3(256), 0, c->stream, pt,
                            (const uint32_t*)G->d_index.p, G->index_slots, pg, in.packed, in.base_off, in.read_len,
                            (const uint32_t*)b.var.p, (const uint32_t*)b.elem_off.p, b.n, b.r0, b.var_bytes, (unsigned long long*)ctr.p);
@@ -800,24 +815,67 @@ int paths_verify_typed(dfk_ctx* c, HostGraph* G, PathState* P, const Inputs& in,
     HIP_TRY(hipMemcpyAsync(out, ctr.p, 8 * PV_N, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->release(ctr);
+    if (!digest) return 0;
+    const unsigned dgrid = 32u * cus;                                           // (a slot pair per block, then the fold: see k_paths_digest)
+    DevBuf dg; rc = c->alloc(dg, 32 + 16ull * dgrid, "paths digest", Place::Low); if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(dg.p, 0, 32 + 16ull * dgrid, c->stream));
+    unsigned long long* slots = (unsigned long long*)dg.p + 4;
+    for (const PathBatch& b : batches)
+        hipLaunchKernelGGL(k_paths_digest, dim3(grid_256(b.n, cus)), dim3(256), 0, c->stream, (const uint32_t*)b.var.p,
+                           (const uint32_t*)b.elem_off.p, b.n, b.r0, b.var_bytes, slots);
+    hipLaunchKernelGGL(k_paths_digest_fold, dim3(1), dim3(256), 0, c->stream, (const unsigned long long*)slots, dgrid, (unsigned long long*)dg.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(digest, dg.p, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->release(dg);
     return 0;
 }
 
 PathState* built_paths(dfk_ctx* c);
-int paths_verify_any(dfk_ctx* c, const Inputs& in, uint64_t* out)
+// what a verify needs of the context: paths built (for the graph's tables) and the k-mer index still held
+int verify_state(dfk_ctx* c)
 {
+    if (!built_paths(c)) return fail(DFK_E_STATE, "no paths: call dfk_paths_build");
+    if (!graph_of(c)->d_index.p) return fail(DFK_E_STATE, "the graph's k-mer index was given back by dfk_paths_index_write / dfk_dups_write: verify before them");
+    return 0;
+}
+// given: the batches of dfk_paths_verify_arrays, of any number of reads (null: the context's own paths, of the reads pathed)
+int paths_verify_any(dfk_ctx* c, const Inputs& in, uint64_t* out, const std::vector<PathBatch>* given = nullptr, uint64_t* digest = nullptr)
+{
+    if (int rc = verify_state(c)) return rc;
     PathState* P = built_paths(c);
-    if (!P) return fail(DFK_E_STATE, "no paths: call dfk_paths_build");
     HostGraph* G = graph_of(c);
-    if (!G->d_index.p) return fail(DFK_E_STATE, "the graph's k-mer index was given back by dfk_paths_index_write / dfk_dups_write: verify before them");
-    if (in.n_reads != P->n_reads) return fail(DFK_E_ARG, "verify: %llu reads given, %llu pathed", (unsigned long long)in.n_reads, (unsigned long long)P->n_reads);
+    if (!given && in.n_reads != P->n_reads) return fail(DFK_E_ARG, "verify: %llu reads given, %llu pathed", (unsigned long long)in.n_reads, (unsigned long long)P->n_reads);
+    const std::vector<PathBatch>& batches = given ? *given : P->batches;
     try {
         switch (c->cfg.K) {
-        case 40: return paths_verify_typed<40>(c, G, P, in, out);
-        case 48: return paths_verify_typed<48>(c, G, P, in, out);
-        default: return paths_verify_typed<60>(c, G, P, in, out);
+        case 40: return paths_verify_typed<40>(c, G, P, in, batches, out, digest);
+        case 48: return paths_verify_typed<48>(c, G, P, in, batches, out, digest);
+        default: return paths_verify_typed<60>(c, G, P, in, batches, out, digest);
         }
     } catch (const std::runtime_error& e) { return fail(DFK_E_HIP, "%s", e.what()); }
+}
+
+// a host caller's reads on the device (outside the arena, as dfk_paths_verify always took them) for one paths_verify_any
+int verify_host_reads(dfk_ctx* c, const uint8_t* packed, const uint64_t* base_off, const uint32_t* read_len, uint64_t n_reads, uint64_t* out,
+                      const std::vector<PathBatch>* given, uint64_t* digest)
+{
+    uint64_t pb = 0;
+    if (n_reads) { const int r1 = host_read(c, &pb, (const char*)base_off + 8 * n_reads, 8); if (r1) return r1; }
+    void* d[3] = {};
+    int rc = 0;
+    auto up = [&](void** dp, const void* h, size_t bytes) {
+        if (rc) return;
+        if (hipMalloc(dp, bytes + 64) != hipSuccess) { (void)hipGetLastError(); rc = fail(DFK_E_NOMEM, "no room on the device for %zu bytes of input", bytes); return; }
+        rc = upload(c, *dp, h, bytes);
+    };
+    up(&d[0], packed, pb); up(&d[1], base_off, n_reads ? (n_reads + 1) * 8 : 0); up(&d[2], read_len, n_reads * 4);   // (no reads: the tables may be null)
+    if (!rc) {
+        Inputs in{(const uint8_t*)d[0], pb, (const uint64_t*)d[1], (const uint32_t*)d[2], nullptr, 0, nullptr, nullptr, n_reads};
+        rc = paths_verify_any(c, in, out, given, digest);
+    }
+    for (void* p : d) (void)hipFree(p);
+    return rc;
 }
 
 PathState* built_paths(dfk_ctx* c)
@@ -1117,21 +1175,53 @@ int dfk_paths_verify(dfk_ctx* c, const uint8_t* packed, const uint64_t* base_off
     if (!c || !out) return fail(DFK_E_ARG, "null argument");
     if (n_reads && (!packed || !base_off || !read_len)) return fail(DFK_E_ARG, "null input array");
     HIP_TRY(hipSetDevice(c->device));
-    uint64_t pb = 0;
-    if (n_reads) { const int r1 = host_read(c, &pb, (const char*)base_off + 8 * n_reads, 8); if (r1) return r1; }
-    void* d[3] = {};
-    int rc = 0;
-    auto up = [&](void** dp, const void* h, size_t bytes) {
-        if (rc) return;
-        if (hipMalloc(dp, bytes + 64) != hipSuccess) { (void)hipGetLastError(); rc = fail(DFK_E_NOMEM, "no room on the device for %zu bytes of input", bytes); return; }
-        rc = upload(c, *dp, h, bytes);
-    };
-    up(&d[0], packed, pb); up(&d[1], base_off, (n_reads + 1) * 8); up(&d[2], read_len, n_reads * 4);
-    if (!rc) {
-        Inputs in{(const uint8_t*)d[0], pb, (const uint64_t*)d[1], (const uint32_t*)d[2], nullptr, 0, nullptr, nullptr, n_reads};
-        rc = paths_verify_any(c, in, out);
+    return verify_host_reads(c, packed, base_off, read_len, n_reads, out, nullptr, nullptr);
+    });
+}
+
+// The verifier on paths given as host arrays: the batches laid out as k_path_emit leaves them (layout_batch), each with its r0,
+// then k_path_verify on the context's graph, k-mer index and tables as dfk_paths_verify launches it, and the paths digest over
+// the same batches.  Edge ids and offsets go to the device as they are: counting them is the kernel's work, and no host array is
+// indexed by either.
+int dfk_paths_verify_arrays(dfk_ctx* c, const uint8_t* packed, const uint64_t* base_off, const uint32_t* read_len, uint64_t n_reads,
+                            const int32_t* offsets, const uint64_t* first, const int32_t* edges, uint64_t reads_per_batch, uint64_t* out)
+{
+    return guarded([&]() -> int {
+    const uint64_t N = n_reads;
+    if (!c || !out || !first || (N && (!packed || !base_off || !read_len || !offsets))) return fail(DFK_E_ARG, "null argument");
+    if (int rc = verify_state(c)) return rc;
+    if (N >= (1ull << 31)) return fail(DFK_E_ARG, "%llu reads: 2^31 - 1 at most", (unsigned long long)N);
+    if (first[0] != 0) return fail(DFK_E_ARG, "the paths do not start at 0");
+    for (uint64_t i = 0; i < N; ++i) if (first[i + 1] < first[i]) return fail(DFK_E_ARG, "the paths' starts fall at read %llu", (unsigned long long)i);
+    if (first[N] >= (1ull << 31)) return fail(DFK_E_ARG, "%llu path edges: 2^31 - 1 at most", (unsigned long long)first[N]);
+    if (first[N] && !edges) return fail(DFK_E_ARG, "null argument");
+    const uint64_t per = reads_per_batch ? reads_per_batch : std::max<uint64_t>(1, N);
+    for (uint64_t r0 = 0; r0 < N; r0 += per) {
+        const uint64_t n = std::min(per, N - r0), bytes = 8 * n + 4 * (first[r0 + n] - first[r0]);
+        if (bytes >= (1ull << 32)) return fail(DFK_E_ARG, "a batch of %llu reads holds %llu bytes of paths: its offsets keep 32 bits", (unsigned long long)n, (unsigned long long)bytes);
     }
-    for (void* p : d) (void)hipFree(p);
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<PathBatch> batches;
+    const uint64_t mark = c->alloc_seq;
+    auto body = [&]() -> int {
+        int rc;
+        std::vector<uint32_t> var, off;
+        for (uint64_t r0 = 0; r0 < N; r0 += per) {
+            PathBatch B; B.r0 = r0; B.n = std::min(per, N - r0); B.file_base = 24 + 8 * r0 + 4 * first[r0];
+            layout_batch(first, edges, offsets, r0, B.n, var, off);
+            B.var_bytes = var.size() * 4;
+            if ((rc = upload_vec(c, B.var, var, "a.paths data")) || (rc = upload_vec(c, B.elem_off, off, "a.paths offsets"))) return rc;
+            batches.push_back(B);
+        }
+        uint64_t res[PV_N + 2] = {};
+        if ((rc = verify_host_reads(c, packed, base_off, read_len, N, res, &batches, res + PV_N))) return rc;
+        for (int i = 0; i < PV_N + 2; ++i) out[i] = res[i];
+        return 0;
+    };
+    int rc;
+    try { rc = body(); } catch (const std::runtime_error& e) { rc = fail(DFK_E_HIP, "%s", e.what()); }
+    (void)hipStreamSynchronize(c->stream);
+    c->release_since(mark);                                                  // the batches
     return rc;
     });
 }

@@ -28,7 +28,7 @@ EXPORTS = [
     "dfk_shard_adj_answer", "dfk_shard_adj_apply", "dfk_graph_build", "dfk_graph_stats", "dfk_graph_write",
     "dfk_shard_dict_share", "dfk_shard_dict_adopt", "dfk_shard_dict_whole",
     "dfk_paths_build", "dfk_paths_build_device", "dfk_paths_stats", "dfk_paths_write", "dfk_paths_fetch", "dfk_paths_index_write", "dfk_dups_write", "dfk_paths_index_dups_write",
-    "dfk_paths_digest", "dfk_paths_verify", "dfk_paths_verify_device", "dfk_pbf_run", "dfk_pbf_result", "dfk_pbf_free",
+    "dfk_paths_digest", "dfk_paths_verify", "dfk_paths_verify_device", "dfk_paths_verify_arrays", "dfk_pbf_run", "dfk_pbf_result", "dfk_pbf_free",
     "dfk_paths_var_bytes", "dfk_paths_write_part", "dfk_shard_pidx_pairs", "dfk_shard_pidx_write", "dfk_shard_dup_keys", "dfk_shard_dup_answer", "dfk_shard_dup_write",
     "dfk_bads_sums", "dfk_bads_write", "dfk_bads_write_part",
     "dfk_hops_build", "dfk_hops_build_bci", "dfk_hops_build_arrays", "dfk_hops_stats", "dfk_hops_fetch", "dfk_hops_write",
@@ -410,6 +410,28 @@ class Dfk:
         _check(lib().dfk_paths_verify_device(self._ctx, C.c_void_p(packed.data_ptr()), C.c_uint64(packed.numel()), C.c_void_p(base_off.data_ptr()),
                                              C.c_void_p(read_len.data_ptr()), C.c_uint64(read_len.numel()), out))
         return {k: int(out[i]) for i, k in enumerate(VERIFY)}
+
+    def paths_verify_arrays(self, packed, base_off, read_len, paths, reads_per_batch=0):
+        """dfk_paths_verify_arrays: the verifier over paths given as [(offset, [edges])...], one per read (or as the tuple paths()
+        returns), cut into batches of reads_per_batch (0 = one).  -> ({counter: value}, (PATHS_SUM, PATHS_XOR) of those paths).
+        Offsets and edge ids are taken modulo 2^32, as the file's words hold them."""
+        packed = np.ascontiguousarray(packed, np.uint8); base_off = np.ascontiguousarray(base_off, np.uint64)
+        read_len = np.ascontiguousarray(read_len, np.uint32)
+        if isinstance(paths, tuple):
+            offsets, first, edges = paths
+        else:
+            offsets = np.array([o for o, _ in paths], np.int64).astype(np.uint32).view(np.int32)
+            first = np.zeros(len(paths) + 1, np.uint64)
+            first[1:] = np.cumsum([len(p) for _, p in paths], dtype=np.uint64)
+            edges = np.array([e for _, p in paths for e in p], np.int64).astype(np.uint32).view(np.int32)
+        offsets = np.ascontiguousarray(offsets, np.int32); first = np.ascontiguousarray(first, np.uint64)
+        edges = np.ascontiguousarray(edges if len(edges) else [0], np.int32)
+        assert len(offsets) == len(read_len) == len(first) - 1
+        room = lambda a: a if len(a) else np.zeros(1, a.dtype)               # (no reads: still arrays, not NULL)
+        out = (C.c_uint64 * 10)()
+        _check(lib().dfk_paths_verify_arrays(self._ctx, _p(room(packed)), _p(base_off if len(read_len) else np.zeros(1, np.uint64)), _p(room(read_len)),
+                                             C.c_uint64(len(read_len)), _p(room(offsets)), _p(first), _p(edges), C.c_uint64(reads_per_batch), out))
+        return {k: int(out[i]) for i, k in enumerate(VERIFY)}, (int(out[8]), int(out[9]))
 
     def paths(self):
         """-> (offsets i32[n], first_edge u64[n+1], edges i32[...])"""

@@ -1,7 +1,10 @@
-"""dfk_paths_digest and dfk_paths_verify (include/dfk.h) pinned where an answer exists: on the seven reference-written fixtures
+"""dfk_paths_digest and dfk_paths_verify (include/dfk.h) pinned where an answer exists: on the eleven reference-written fixtures
 the device verifier's eight counters are the ones oracle/verify_oracle.py computes from the reference's files, and the digests
-are the ones those files give -- under several pass and batch geometries.  tests/test_gpu_fullsize_graph.py then uses both where
-no oracle runs."""
+are the ones those files give -- each under three geometries: the default; three count passes with 1500 instances an item; two
+part slots a read and no filter in front of the index (every batch pathed twice).  Every fixture is pathed in ONE batch here and
+its paths are correct, so broken, no_anchor and dict_bad are 0 throughout: tests/test_gpu_verify_damaged.py shows the verifier
+damaged paths, damaged reads and batches with r0 > 0.  Then 2 x 300-base reads (verifier counters as invariants only) and the
+offset tables dfk_paths_build refuses.  tests/test_gpu_fullsize_graph.py uses digests and verifier where no oracle runs."""
 import os
 
 import numpy as np
