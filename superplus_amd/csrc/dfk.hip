@@ -364,6 +364,7 @@ ScanSwitches scan_switches()
     if (const char* e = getenv("DFK_SCAN_KEY_PIECE")) { sw.key_piece_set = true; sw.key_piece = strtoull(e, nullptr, 10); }
     if (const char* e = getenv("DFK_SCAN_KEY_TAIL")) sw.key_tail = strtoull(e, nullptr, 10);
     sw.no_overlap = getenv("DFK_NO_OVERLAP") != nullptr;
+    sw.no_keys = getenv("DFK_SCAN_NO_KEYS") != nullptr;
     return sw;
 }
 
@@ -430,7 +431,8 @@ int scan_keys_piece(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, ui
     ScanKeys sk{(uint32_t*)J->keys.p + (uint64_t)sl * P.cap * P.n_cls, (unsigned long long*)J->fill.p + (uint64_t)sl * P.n_cls, P.cap, P.ib};
     if (step.wait_slice_reader) HIP_TRY(hipStreamWaitEvent(c->stream, J->ev_part[sl], 0));
     HIP_TRY(hipMemsetAsync(sk.fill, 0, P.n_cls * 8, c->stream));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, true>), dim3(grid), dim3(PART_THREADS), scan_lds(P), c->stream,
+    if (J->pp.log2_world != 0) return fail(DFK_E_STATE, "run keys are built on one rank only");
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, true, true>), dim3(grid), dim3(PART_THREADS), scan_lds(P), c->stream,
                        in.packed, in.packed_bytes, in.base_off, (const uint32_t*)c->good_len.p, r0, r1, J->pp,
                        (unsigned long long*)T->acc.p, (unsigned long long*)nullptr, (unsigned long long*)J->d_n.p, P.ovf_cap,
                        (uint32_t*)J->ovf_tmp.p, (uint4*)T->summ.p, (uint32_t*)T->classes.p, sk);
@@ -481,7 +483,9 @@ int scan_range(dfk_ctx* c, const Inputs& in, BucketTable* T, ScanJob* J, uint64_
         // (ms_part_count runs until the bucket totals exist)
         if (r1 == in.n_reads && J->count_due) { int rc = scan_keys_count(c, T, J); if (rc) return rc; }
     } else if (P.register_scan) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_count<K, 16, false>), dim3(grid), dim3(PART_THREADS), scan_lds(P), c->stream,
+        // (one rank: bucket_of without the owner interleave, chosen here once per launch)
+        auto* scan = pp.log2_world == 0 ? k_scan_count<K, 16, false, true> : k_scan_count<K, 16, false, false>;
+        hipLaunchKernelGGL(scan, dim3(grid), dim3(PART_THREADS), scan_lds(P), c->stream,
                            in.packed, in.packed_bytes, in.base_off, (const uint32_t*)c->good_len.p, r0, r1, pp,
                            (unsigned long long*)T->acc.p, (unsigned long long*)T->class_hist.p, (unsigned long long*)J->d_n.p, P.ovf_cap,
                            (uint32_t*)J->ovf_tmp.p, (uint4*)T->summ.p, (uint32_t*)T->classes.p, ScanKeys{});

@@ -153,6 +153,13 @@ __device__ __forceinline__ uint32_t bucket_of(uint32_t minhash, const PartParams
     const uint32_t b = (minhash * 0x9E3779B1u) >> (32 - pp.log2_nb);
     return ((b & ((1u << pp.log2_world) - 1u)) << (pp.log2_nb - pp.log2_world)) | (b >> pp.log2_world);
 }
+// the same with the owner interleave decided at compile time: one rank (log2_world == 0) has none
+template <bool ONE_RANK>
+__device__ __forceinline__ uint32_t bucket_of(uint32_t minhash, const PartParams& pp)
+{
+    if constexpr (ONE_RANK) return (minhash * 0x9E3779B1u) >> (32 - pp.log2_nb);
+    else return bucket_of(minhash, pp);
+}
 constexpr int PART_QCAP = 8;          // queued records per lane before an early flush
 
 template <int K>
@@ -444,8 +451,10 @@ __device__ __forceinline__ void static_for(F&& f)
 // (ScanKeys, SCAN_STAGE, KEY_SUB_BITS and the scan's LDS sizes: dfk_scan_plan.h)
 constexpr uint32_t KEY_TILE = 4096;   // keys a partition block holds in registers and reserves room for at once (one atomic per sub-slice present)
 
-template <int K, int M, bool KEYS>
-__global__ void __launch_bounds__(PART_THREADS)
+// ONE_RANK: the launch has log2_world == 0, and bucket_of drops the owner interleave.
+// (The second launch bound is waves per SIMD: five at K = 40, four above, which the register allocator otherwise gives up at K = 60.)
+template <int K, int M, bool KEYS, bool ONE_RANK>
+__global__ void __launch_bounds__(PART_THREADS, K <= 40 ? 5 : 4)
 k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const uint64_t* __restrict__ base_off,
              const uint32_t* __restrict__ good_len, uint64_t r_first, uint64_t n_reads /* reads [r_first, n_reads) */, PartParams pp,
              unsigned long long* __restrict__ bucket_acc, unsigned long long* __restrict__ class_hist,
@@ -453,10 +462,10 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
              uint4* __restrict__ summaries, uint32_t* __restrict__ read_classes, ScanKeys sk)
 {
     constexpr int W = K - M + 1;
-    constexpr uint32_t mmask = M == 16 ? 0xFFFFFFFFu : ((1u << (2 * M)) - 1u);
-    constexpr uint32_t rsh = 2 * (M - 1);
     constexpr int RUNS = SUMMARY_RUNS;                                   // buckets a lane remembers per read: as many as a summary holds
     static_assert(KTraits<K>::NK_MAX < 64, "nk takes the key's six low bits");
+    static_assert(M == 16, "an m-mer is one 32-bit window of the read's 2-bit stream");
+    static_assert(2 * PART_THREADS == 256, "a lane's slot cursor is 2 * tid + 256 * (runs closed)");
     extern __shared__ uint32_t smem[];
     uint32_t* runb = smem;                                               // [RUNS][PART_THREADS] bucket of each closed run
     uint16_t* runf = reinterpret_cast<uint16_t*>(runb + RUNS * PART_THREADS);   // [RUNS][PART_THREADS] its summary field: nk | rel << 6
@@ -503,7 +512,9 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
         const uint64_t r = r0 + tid;
         const uint32_t gl = r < n_reads ? good_len[r] : 0;
         const bool live = gl >= (uint32_t)K + 1;                         // Kmerizer::map: len < K+1 emits nothing (:153)
-        uint32_t qn = 0, cmask = 0;
+        // the slot the next closed run takes, as the byte offset of its field in runf: 2 * tid + 2 * PART_THREADS * (runs closed).
+        // Twice that is the byte offset of its bucket in runb, and 2 * tid < 256 leaves the run count in the bits from 8 up.
+        uint32_t qslot = 2u * (uint32_t)tid, cmask = 0;
         uint64_t sum_lo = 0, sum_hi = 0;
         if (live) {
             const uint64_t bit0 = base_off[r] * 8;
@@ -523,14 +534,19 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
             uint64_t nbit = bit0 + 2 * (M - 1);                          // the first bit of the next block's bases
             uint32_t nw[NW];
             load(nbit, nw);                                              // block 0's words, in flight during the prologue
-            uint32_t f = 0, rc = 0;
+            // The reverse-complement m-mer that ends at a base is the complement of the 32 stream bits that end with that base
+            // (base j sits at bits 2j, the newest base on top), so it is cut out of the block's aligned words at a constant
+            // place -- no chain from base to base -- and its top two bits are the base the forward m-mer shifts in.
+            // `before` is the 32 stream bits in front of the block: the window at the last position of the block before it.
+            uint32_t f = 0, before;
             {
                 // the first M-1 bases: 2M-2 = 30 bits from a byte offset
                 const uint64_t wi = bit0 >> 5;
                 const uint32_t w0 = words[wi < n_words ? wi : n_words - 1], w1 = words[wi + 1 < n_words ? wi + 1 : n_words - 1];
                 const uint32_t pw = alignbit(wi + 1 < n_words ? w1 : 0u, wi < n_words ? w0 : 0u, (uint32_t)bit0 & 31u);
 #pragma unroll
-                for (int j = 0; j < M - 1; ++j) { const uint32_t b = (pw >> (2 * j)) & 3u; f = ((f << 2) | b) & mmask; rc = (rc >> 2) | ((3u - b) << rsh); }
+                for (int j = 0; j < M - 1; ++j) f = (f << 2) | ((pw >> (2 * j)) & 3u);
+                before = pw << 2;                                        // (bits 0, 1 belong to no window)
             }
             const uint32_t n_mmers = gl - M + 1;                         // m-mer positions t = 0 .. n_mmers-1; k-mer s = t-W+1 is complete at t >= W-1
             // suffix minima of the previous block, overwritten by the hashes of this one -- and where they sit, a BYTE each, four
@@ -542,12 +558,18 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
             auto sidx_set = [&](int i, uint32_t v) { const uint32_t sh = 8u * (uint32_t)(i & 3); sidxw[i >> 2] = (sidxw[i >> 2] & ~(255u << sh)) | (v << sh); };
 #pragma unroll
             for (int i = 0; i < (W + 3) / 4; ++i) sidxw[i] = 0;
-            uint32_t P = 0, Pi = 0;
+            // the prefix minimum, and where it sits plus PB.  With PB = W one select and one subtraction give a run's `rel`
+            // from either minimum; where bi + W no longer fits an inline constant (K = 60) every such constant would take a
+            // register, and PB = 0 keeps the two forms apart.  (K = 60 sits at its 128 registers either way; which form stays
+            // clear of scratch there is what `make asm` showed: PB = W without keys -- 96 registers -- and PB = 0 with them.)
+            constexpr int PB = (2 * W - 1 <= 65 || !KEYS) ? W : 0;
+            uint32_t P = 0, PiW = 0;
             uint32_t cur_b = 0, cur_nk = 0, cur_rel = 0;
             auto close_run = [&]() {                                     // (cheap on purpose: see the head of this kernel)
-                if (qn < (uint32_t)RUNS) {
-                    runb[qn * PART_THREADS + tid] = cur_b;
-                    runf[qn * PART_THREADS + tid] = (uint16_t)(cur_nk | (cur_rel << 6));
+                if (qslot < 2u * RUNS * PART_THREADS) {
+                    // runb[qn * PART_THREADS + tid] and runf[qn * PART_THREADS + tid]: one shift and two constant offsets
+                    *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(runb) + 2u * qslot) = cur_b;
+                    *reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(runf) + qslot) = (uint16_t)(cur_nk | (cur_rel << 6));
                 } else {
                     // the eleventh run and beyond (two reads in 10^5 have them; the read then goes through the scanning scatter):
                     // counted on the spot
@@ -555,7 +577,7 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
                     else atomicAdd(&bucket_acc[cur_b], (1ull << 32) | cur_nk);
                     cmask |= 1u << sweep_class_of(cur_b & ((1u << log2_local) - 1u), log2_local);
                 }
-                ++qn;
+                qslot += 2u * PART_THREADS;
             };
             for (uint32_t t0 = 0; t0 < n_mmers; t0 += W) {              // one block of W m-mer positions; t = t0 + bi
                 // this block's bases, aligned so that base bi is bits 2bi, 2bi+1 of the NA words; then the next block's loads
@@ -572,22 +594,30 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
                 static_for<0, W>([&](auto bi_c) {
                     constexpr int bi = decltype(bi_c)::value;
                     if (t0 + (uint32_t)bi < n_mmers) {
-                        const uint32_t b = (a[(2 * bi) >> 5] >> ((2 * bi) & 31)) & 3u;
-                        f = ((f << 2) | b) & mmask;
-                        rc = (rc >> 2) | ((3u - b) << rsh);
+                        // the 32 stream bits that end with base bi: bits [2 bi + 2, 2 bi + 34) of before | a[0] | a[1] | ...
+                        constexpr int wq = (2 * bi + 2) >> 5, ws = (2 * bi + 2) & 31;
+                        const uint32_t wlo = wq == 0 ? before : a[wq > 0 ? wq - 1 : 0];
+                        const uint32_t win = ws == 0 ? wlo : alignbit(a[wq < NA ? wq : NA - 1], wlo, ws);
+                        f = alignbit(f, win, 30);                        // (f << 2) | the base
+                        const uint32_t rc = ~win;
                         const uint32_t h = mmer_hash(f < rc ? f : rc);
+                        if constexpr (bi == W - 1) before = win;
                         const bool newmin = bi == 0 || h < P;
                         P = newmin ? h : P;
-                        Pi = newmin ? (uint32_t)bi : Pi;
+                        PiW = newmin ? (uint32_t)(bi + PB) : PiW;
                         const bool first = t0 == 0;                      // (with bi == W-1: the read's first k-mer)
                         if (!first || bi == W - 1) {                      // a k-mer ends here
                             uint32_t mv = P;
                             bool older = false;
                             if constexpr (bi != W - 1) { older = arr[bi + 1] < mv; mv = older ? arr[bi + 1] : mv; }
-                            const uint32_t bucket = bucket_of(mv, pp);
+                            const uint32_t bucket = bucket_of<ONE_RANK>(mv, pp);
                             const bool open = first || bucket != cur_b || cur_nk == (uint32_t)KTraits<K>::NK_MAX;
                             if (open && !first) close_run();
-                            const uint32_t rel = (bi != W - 1 && older) ? sidx_get(bi + 1 < W ? bi + 1 : 0) - (uint32_t)bi - 1u : (uint32_t)(W - 1 - bi) + Pi;
+                            // the minimizer's offset from this k-mer's first m-mer, position bi + 1 - W of this block: an older
+                            // one sits at sidx[bi + 1] of the block before, the prefix minimum at PiW - PB of this one
+                            uint32_t rel;
+                            if constexpr (PB == W) rel = ((bi != W - 1 && older) ? sidx_get(bi + 1 < W ? bi + 1 : 0) : PiW) - (uint32_t)(bi + 1);
+                            else rel = (bi != W - 1 && older) ? sidx_get(bi + 1 < W ? bi + 1 : 0) - (uint32_t)bi - 1u : (uint32_t)(W - 1 - bi) + PiW;
                             cur_rel = open ? rel : cur_rel;
                             cur_nk = open ? 1u : cur_nk + 1u;
                             cur_b = open ? bucket : cur_b;
@@ -608,6 +638,7 @@ k_scan_count(const uint8_t* __restrict__ packed, uint64_t packed_bytes, const ui
         }
         // ---- the runs' buckets: counters and class mask, all lanes together (a read has ~4 runs)
         // (KEYS: the whole block walks the runs together, so that a full stage can be flushed between two of them)
+        const uint32_t qn = qslot >> 8;                                  // runs closed
         const uint32_t mine = min(qn, (uint32_t)RUNS);
         for (uint32_t i = 0; KEYS ? __syncthreads_or(i < mine) != 0 : __ballot(i < mine) != 0ull; ++i) {
             const bool has = i < mine;

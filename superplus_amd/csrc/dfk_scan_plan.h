@@ -48,13 +48,14 @@ constexpr uint64_t SCAN_TAIL_READS = 32ull << 20;   // the last piece of a keyed
 constexpr uint64_t KEY_SCRATCH_MAX = 16ull << 30;   // most the keys' copies may take
 constexpr uint32_t SCAN_BLOCKS_PER_CU = 128;        // of a grid-stride scan (12 blocks per CU: 57 ms per 225 M reads, 128: 47 ms)
 
-// DFK_SCAN_KEY_PIECE, DFK_SCAN_KEY_TAIL, DFK_NO_OVERLAP: read once per scan (tests switch them within one process);
-// DFK_SCAN_BLOCKS (blocks per CU of a scan's grid, 0 = unset): once per process.  scan_switches (dfk.hip) reads the four.
+// DFK_SCAN_KEY_PIECE, DFK_SCAN_KEY_TAIL, DFK_NO_OVERLAP, DFK_SCAN_NO_KEYS: read once per scan (tests switch them within one
+// process); DFK_SCAN_BLOCKS (blocks per CU of a scan's grid, 0 = unset): once per process.  scan_switches (dfk.hip) reads the five.
 struct ScanSwitches {
     bool key_piece_set = false; uint64_t key_piece = 0;   // set: the scan is keyed whatever its reads, in pieces of at most this
     uint64_t key_tail = SCAN_TAIL_READS;                  // 0: equal pieces
     uint32_t scan_blocks = 0;
     bool no_overlap = false;
+    bool no_keys = false;                                 // DFK_SCAN_NO_KEYS: the scan keeps its atomics whatever its reads (tests: the unkeyed kernel at every K)
 };
 
 struct ScanInputs {
@@ -97,7 +98,7 @@ inline ScanPlan plan_scan(const ScanInputs& in)
     // four or more (at 2 x 100 bp: K=40, 5.7 runs a read, the scan 505 -> 409 ms; K=48, 4.1, 368 -> 333); at K=60 (2.8)
     // the counting kernels cost more than the atomics they replace (284 -> 313 ms), and the scan keeps its atomics
     const double runs = in.n_reads ? 1.0 + 2.0 * std::max(0.0, 4.0 * (double)in.packed_bytes / (double)in.n_reads - in.K + 1) / (in.W + 1) : 0.0;
-    p.keyed = !in.by_class && in.register_scan && in.n_reads && (runs >= 3.5 || in.sw.key_piece_set);
+    p.keyed = !in.by_class && in.register_scan && in.n_reads && (runs >= 3.5 || in.sw.key_piece_set) && !in.sw.no_keys;
     if (!p.keyed) return p;
     const uint32_t cb = std::min<uint32_t>(6, in.log2_nb);
     p.ib = in.log2_nb - cb; p.n_cls = 1u << cb;
