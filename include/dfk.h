@@ -418,6 +418,68 @@ int dfk_subset_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_SUBSET_WORDS] */);
 int dfk_subset_fetch(dfk_ctx* ctx, uint64_t* ids, uint64_t ids_cap, uint64_t* n_ids, uint64_t* eoi, uint64_t eoi_cap, uint64_t* n_eoi);
 int dfk_subset_write(dfk_ctx* ctx, const char* dir);
 
+/* ---- the fourth step of the patching stage: the gap closers' read sets per edge (CloseGap2, 10X/Closomatic.cc:503-552; Stackster,
+ * 10X/Stackster.cc:289-324) ----
+ * For every pair StagePatch calls both closers (RunStages.cc:276-309), and both begin by walking paths_index[f], f in {e, inv[e]},
+ * for e = e1 and e = inv[e2], fetching every listed read's path and working out where it lies against the edge.  That front end is
+ * all they take from paths and paths_index; it depends on e alone, so it is built once per CLOSER EDGE -- ce = the ascending
+ * distinct {first, inv[second]} over the pairs -- and not per pair:
+ *   locs(e)     CloseGap2's locs[ei] in the reference's order: (id, pos, fw), pos = offset - k-mers of the edges before the occurrence
+ *   anchors(e)  the distinct (g, add) of its prec with MIN_EDGE_COUNT = 5 occurrences or more, with their counts, ascending
+ *   reads(e)    Stackster's idsfw for spass 1 (ALT = False): sorted distinct id << 1 | fw, duplicates (dup[id / 2]) left out, mates
+ *               within MAX_DIST = 800 let in.  A pair takes reads(e1) U {(id, !fw) : (id, fw) in reads(inv[e2])}.
+ * The rule, the plan and the files' layouts are stated in csrc/dfk_closer.h.  Nothing that needs bases or qualities is made.
+ *   dfk_closer_build    pairs NULL: the context's own dfk_hops_build* result (DFK_E_STATE without one).  Otherwise n_pairs x (i32, i32).
+ *                       dup: n_reads / 2 host bytes, a.dup's payload, required.  The result stays in host memory with the paths.
+ *   dfk_closer_build_arrays  the same stage on host arrays, for tests that choose graph, paths, offsets, pairs and marks; K is the
+ *                       context's.  reads_per_batch 0 = one batch.  With dir the four files are written there.  Its result is what
+ *                       dfk_closer_stats / _fetch / _write serve until the next dfk_closer_build*.
+ *   dfk_closer_stats    out[DFK_CLOSER_WORDS]: the counters below
+ *   dfk_closer_fetch    ce, and each table's starts ([n_edges + 1] words, or NULL) and records (locs: 2 u64 a record, {id, pos | fw << 32};
+ *                       anchors: 3 i32; reads: u64).  A NULL buffer with cap 0 = that count alone; a buffer too small: DFK_E_ARG
+ *   dfk_closer_write    into dir (which must exist), all four or none.  Little-endian, no byte undefined:
+ *                         a.close.edges    "BINWRITE" | u64 n | n x u64
+ *                         the tables       magic[8] | u64 n | (n + 1) x u64 starts | the records; element k belongs to ce[k]
+ *                         a.close.locs     "DFKCLOC1", 16-byte records {i64 id, i32 pos, u32 fw}
+ *                         a.close.anchors  "DFKCANC1", 12-byte records {i32 g, i32 add, i32 count}
+ *                         a.close.reads    "DFKCRDS1",  8-byte records id << 1 | fw
+ * Built a range of ce ranks at a time (DFK_PIDX_RANGE_PAIRS forces small ranges): neither table is ever whole on the device.
+ * Valid from dfk_paths_build until the paths are dropped, before or after dfk_paths_index_write / dfk_dups_write / dfk_bads_write;
+ * otherwise DFK_E_STATE.  A refused call changes nothing and an earlier result is still served: an edge id outside [0, E), an odd
+ * number of reads, a read id of 2^31 or more, one edge with 2^32 records or more, dup NULL are DFK_E_ARG.  Not for the ranks of a
+ * sharded run. */
+#define DFK_CLOSER_WORDS 24
+#define DFK_CLOSER_N_EDGES 0         /* closer edges */
+#define DFK_CLOSER_N_LOCS 1          /* locs records */
+#define DFK_CLOSER_N_ANCHORS 2
+#define DFK_CLOSER_N_READS 3         /* set entries */
+#define DFK_CLOSER_PREC 4            /* prec tuples seen */
+#define DFK_CLOSER_MATES_IN 5        /* mates let in (Stackster.cc:322, before UniqueSort) */
+#define DFK_CLOSER_MATES_OUT 6       /* ... and kept out by MAX_DIST (:321) */
+#define DFK_CLOSER_DUP_SKIPPED 7     /* list entries skipped as duplicates (:302) */
+#define DFK_CLOSER_RANGES 8          /* ranges of ce ranks the tables were built in */
+#define DFK_CLOSER_US 9              /* microseconds: the build call, */
+#define DFK_CLOSER_US_MARK 10        /* its marks and ranks, */
+#define DFK_CLOSER_US_WEIGH 11       /* the weights per rank, */
+#define DFK_CLOSER_US_SWEEP 12       /* the ranges' sweeps (counts, scans, records), */
+#define DFK_CLOSER_US_SORT 13        /* their sorts, compactions and copies to the host */
+#define DFK_CLOSER_EDGES_SUM 14      /* sum and xor over positions i of h(i, word) (k_digest_seq): ce as u64 (salt 0x9999), */
+#define DFK_CLOSER_EDGES_XOR 15
+#define DFK_CLOSER_LOCS_SUM 16       /* the locs records as u64 words, two a record (salt 0xAAAA), */
+#define DFK_CLOSER_LOCS_XOR 17
+#define DFK_CLOSER_ANCHORS_SUM 18    /* the anchors records as u32 words, three a record (salt 0xBBBB), */
+#define DFK_CLOSER_ANCHORS_XOR 19
+#define DFK_CLOSER_READS_SUM 20      /* the reads records as u64 (salt 0xCCCC) */
+#define DFK_CLOSER_READS_XOR 21
+int dfk_closer_build(dfk_ctx* ctx, const int32_t* pairs /* 2 per pair, or NULL */, uint64_t n_pairs, const uint8_t* dup /* [n_reads / 2] */);
+int dfk_closer_build_arrays(dfk_ctx* ctx, uint64_t n_edges, const int32_t* inv, const int32_t* kmers, uint64_t n_reads, const uint64_t* first /* [n_reads + 1] */,
+                            const int32_t* edges, const int32_t* offsets /* [n_reads] */, const int32_t* pairs, uint64_t n_pairs, const uint8_t* dup /* [n_reads / 2] */,
+                            uint64_t reads_per_batch, const char* dir /* NULL = no files */);
+int dfk_closer_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_CLOSER_WORDS] */);
+int dfk_closer_fetch(dfk_ctx* ctx, uint64_t* edges, uint64_t edges_cap, uint64_t* n_edges, uint64_t* loc_first, uint64_t* locs, uint64_t locs_cap, uint64_t* n_locs,
+                     uint64_t* anchor_first, int32_t* anchors, uint64_t anchors_cap, uint64_t* n_anchors, uint64_t* read_first, uint64_t* reads, uint64_t reads_cap, uint64_t* n_reads);
+int dfk_closer_write(dfk_ctx* ctx, const char* dir);
+
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).
  * dfk_paths_digest  fills out[DFK_CHECK_WORDS] with digests that depend on the CONTENT of a.paths, a.paths.inv, a.countsb and

@@ -552,7 +552,7 @@ int main(int argc, char** argv)
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
         {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
-        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -578,6 +578,9 @@ int main(int argc, char** argv)
 
     // SUBSET=True (the subset of interest, a.<K>/a.sub.*) works from FindEdgePairs' pairs
     if (truthy(a["SUBSET"]) && !truthy(a["HOPS"])) give_up("SUBSET=True needs HOPS=True: the subset of interest is taken from the edge pairs");
+
+    // CLOSER=True (the gap closers' read sets per edge, a.<K>/a.close.*) works from FindEdgePairs' pairs, the paths and a.dup
+    if (truthy(a["CLOSER"]) && (!truthy(a["HOPS"]) || !truthy(a["PATHS"]))) give_up("CLOSER=True needs HOPS=True and PATHS=True: the closers' read sets are built per edge of the edge pairs, from the paths");
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -1020,6 +1023,24 @@ int main(int argc, char** argv)
                                (unsigned long long)ss[DFK_SUBSET_N_IDS], (unsigned long long)ss[DFK_SUBSET_N_EOI], (unsigned long long)ss[DFK_SUBSET_PATH_ENTRIES],
                                (unsigned long long)ss[DFK_SUBSET_INDEX_ENTRIES], (unsigned long long)ss[DFK_SUBSET_RANGES], (unsigned long long)ss[DFK_SUBSET_IDS_SUM],
                                (unsigned long long)ss[DFK_SUBSET_IDS_XOR], (unsigned long long)ss[DFK_SUBSET_EOI_SUM], (unsigned long long)ss[DFK_SUBSET_EOI_XOR]);
+                    }
+                    if (truthy(a["CLOSER"])) {                                  // the closers' read sets per edge (Closomatic.cc:503-552, Stackster.cc:289-324): a.<K>/a.close.*, after a.hops and a.sub.*
+                        std::vector<uint8_t> dup(n_reads / 2 + 1, 0);          // a.dup as this run wrote it: "BINWRITE", the count, a byte a pair
+                        {
+                            FILE* f = fopen((dir + "/a.dup").c_str(), "rb");
+                            uint64_t head[2] = {0, 0};
+                            const bool ok = f && fread(head, 8, 2, f) == 2 && head[1] == n_reads / 2 && fread(dup.data(), 1, n_reads / 2, f) == n_reads / 2;
+                            if (f) fclose(f);
+                            if (!ok) throw std::runtime_error("cannot read back " + dir + "/a.dup");
+                        }
+                        uint64_t cs[DFK_CLOSER_WORDS] = {};
+                        if (dfk_closer_build(ctx, nullptr, 0, dup.data()) || dfk_closer_write(ctx, dir.c_str()) || dfk_closer_stats(ctx, cs)) throw std::runtime_error(dfk_last_error());
+                        printf("DF_CLOSER {\"edges\": %llu, \"locs\": %llu, \"anchors\": %llu, \"reads\": %llu, \"ranges\": %llu, \"a.close.edges\": \"%016llx%016llx\", \"a.close.locs\": \"%016llx%016llx\", "
+                               "\"a.close.anchors\": \"%016llx%016llx\", \"a.close.reads\": \"%016llx%016llx\"}\n",
+                               (unsigned long long)cs[DFK_CLOSER_N_EDGES], (unsigned long long)cs[DFK_CLOSER_N_LOCS], (unsigned long long)cs[DFK_CLOSER_N_ANCHORS], (unsigned long long)cs[DFK_CLOSER_N_READS],
+                               (unsigned long long)cs[DFK_CLOSER_RANGES], (unsigned long long)cs[DFK_CLOSER_EDGES_SUM], (unsigned long long)cs[DFK_CLOSER_EDGES_XOR], (unsigned long long)cs[DFK_CLOSER_LOCS_SUM],
+                               (unsigned long long)cs[DFK_CLOSER_LOCS_XOR], (unsigned long long)cs[DFK_CLOSER_ANCHORS_SUM], (unsigned long long)cs[DFK_CLOSER_ANCHORS_XOR], (unsigned long long)cs[DFK_CLOSER_READS_SUM],
+                               (unsigned long long)cs[DFK_CLOSER_READS_XOR]);
                     }
                 }
             }

@@ -41,11 +41,14 @@ struct HostGraph {
     void (*paths_free)(struct PathState*) = nullptr;
     struct SubsetResult* subset_arrays = nullptr;                    // dfk_subset_build_arrays' result (dfk_subset.inc)
     void (*subset_free)(struct SubsetResult*) = nullptr;
+    struct CloserResult* closer_arrays = nullptr;                    // dfk_closer_build_arrays' result (dfk_closer.inc)
+    void (*closer_free)(struct CloserResult*) = nullptr;
     ~HostGraph()
     {
         if (paths && paths_free) paths_free(paths);
         if (hops_arrays && paths_free) paths_free(hops_arrays);
         if (subset_arrays && subset_free) subset_free(subset_arrays);
+        if (closer_arrays && closer_free) closer_free(closer_arrays);
     }
 };
 

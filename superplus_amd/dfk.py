@@ -33,6 +33,7 @@ EXPORTS = [
     "dfk_bads_sums", "dfk_bads_write", "dfk_bads_write_part",
     "dfk_hops_build", "dfk_hops_build_bci", "dfk_hops_build_arrays", "dfk_hops_stats", "dfk_hops_fetch", "dfk_hops_write",
     "dfk_subset_build", "dfk_subset_build_arrays", "dfk_subset_stats", "dfk_subset_fetch", "dfk_subset_write",
+    "dfk_closer_build", "dfk_closer_build_arrays", "dfk_closer_stats", "dfk_closer_fetch", "dfk_closer_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -48,6 +49,11 @@ SUBSET_WORDS = 16
 SUBSET = ["eoi", "ids", "path_entries", "index_entries", "ranges", "one_read_only", "us", "us_sweep", "us_gather", "us_index",
           "ids_sum", "ids_xor", "eoi_sum", "eoi_xor"]
 SUBSET_FILES = ("a.sub.ids", "a.sub.eoi", "a.sub.paths", "a.sub.paths.inv")
+# dfk_closer_stats' words (include/dfk.h, DFK_CLOSER_*)
+CLOSER_WORDS = 24
+CLOSER = ["edges", "locs", "anchors", "reads", "prec", "mates_in", "mates_out", "dup_skipped", "ranges", "us", "us_mark", "us_weigh", "us_sweep", "us_sort",
+          "edges_sum", "edges_xor", "locs_sum", "locs_xor", "anchors_sum", "anchors_xor", "reads_sum", "reads_xor"]
+CLOSER_FILES = ("a.close.edges", "a.close.locs", "a.close.anchors", "a.close.reads")
 # dfk_adj_outcome's codes (include/dfk.h, DFK_ADJ_*)
 ADJ_OUTCOMES = ["not applicable", "used", "discarded: guess too low", "discarded: list problem", "no block", "dropped for an allocation",
                 "switched off"]
@@ -390,6 +396,58 @@ class Dfk:
     def subset_write(self, directory):
         """dfk_subset_write: a.sub.ids, a.sub.eoi, a.sub.paths, a.sub.paths.inv into `directory` (which must exist)."""
         _check(lib().dfk_subset_write(self._ctx, None if directory is None else str(directory).encode()))
+
+    def closer_build(self, dup, pairs=None):
+        """dfk_closer_build: the closers' read sets per closer edge.  dup: a byte per PAIR of reads (a.dup's payload); pairs None = the
+        context's own hops result, else int32[n, 2].  Returns closer_stats()."""
+        dup = None if dup is None else np.ascontiguousarray(dup, np.uint8)
+        room_d = dup if dup is None or len(dup) else np.zeros(1, np.uint8)
+        if pairs is None:
+            _check(lib().dfk_closer_build(self._ctx, None, C.c_uint64(0), _p(room_d)))
+        else:
+            pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+            room = pairs if len(pairs) else np.zeros((1, 2), np.int32)      # (an empty list is still a list: NULL would mean the hops result)
+            _check(lib().dfk_closer_build(self._ctx, _p(room), C.c_uint64(len(pairs)), _p(room_d)))
+        return self.closer_stats()
+
+    def closer_build_arrays(self, inv, kmers, paths, offsets, pairs, dup, reads_per_batch=0, directory=None):
+        """dfk_closer_build_arrays: the same stage on arrays (paths: a list of edge lists, one per read, offsets their offset words;
+        pairs: [(e1, e2)]; dup a byte per pair of reads; K is the context's); with a directory the four files a.close.* are written
+        there.  Returns closer_stats()."""
+        inv, kmers = np.ascontiguousarray(inv, np.int32), np.ascontiguousarray(kmers, np.int32)
+        first = np.zeros(len(paths) + 1, np.uint64)
+        first[1:] = np.cumsum([len(p) for p in paths], dtype=np.uint64)
+        edges = np.ascontiguousarray([e for p in paths for e in p] or [0], np.int32)
+        off = np.ascontiguousarray(list(offsets) or [0], np.int32)
+        pr = np.ascontiguousarray(list(pairs) or [(0, 0)], np.int32).reshape(-1, 2)
+        dp = None if dup is None else np.ascontiguousarray(list(dup) or [0], np.uint8)
+        assert len(inv) == len(kmers) and len(offsets) == len(paths)
+        _check(lib().dfk_closer_build_arrays(self._ctx, C.c_uint64(len(inv)), _p(inv), _p(kmers), C.c_uint64(len(paths)), _p(first), _p(edges), _p(off), _p(pr),
+                                             C.c_uint64(len(pairs)), _p(dp), C.c_uint64(reads_per_batch), None if directory is None else str(directory).encode()))
+        return self.closer_stats()
+
+    def closer_stats(self):
+        """dfk_closer_stats: {counter: value} -- closer edges, records, anchors, set entries, prec tuples, mates let in and kept out, list
+        entries skipped as duplicates, ranges, times, digests."""
+        out = (C.c_uint64 * CLOSER_WORDS)()
+        _check(lib().dfk_closer_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(CLOSER)}
+
+    def closer_fetch(self):
+        """dfk_closer_fetch: dict(ce uint64[n], loc_first / anchor_first / read_first uint64[n + 1], locs uint64[m, 2] (id, pos | fw << 32),
+        anchors int32[a, 3] (g, add, count), reads uint64[r] (id << 1 | fw))."""
+        ne, nl, na, nr = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        z = C.c_uint64(0)
+        _check(lib().dfk_closer_fetch(self._ctx, None, z, C.byref(ne), None, None, z, C.byref(nl), None, None, z, C.byref(na), None, None, z, C.byref(nr)))
+        ce, locs, anchors, reads = np.zeros(ne.value, np.uint64), np.zeros((nl.value, 2), np.uint64), np.zeros((na.value, 3), np.int32), np.zeros(nr.value, np.uint64)
+        lf, af, rf = (np.zeros(ne.value + 1, np.uint64) for _ in range(3))
+        _check(lib().dfk_closer_fetch(self._ctx, _p(ce), C.c_uint64(ne.value), C.byref(ne), _p(lf), _p(locs), C.c_uint64(nl.value), C.byref(nl),
+                                      _p(af), _p(anchors), C.c_uint64(na.value), C.byref(na), _p(rf), _p(reads), C.c_uint64(nr.value), C.byref(nr)))
+        return dict(ce=ce, loc_first=lf, locs=locs, anchor_first=af, anchors=anchors, read_first=rf, reads=reads)
+
+    def closer_write(self, directory):
+        """dfk_closer_write: a.close.edges, a.close.locs, a.close.anchors, a.close.reads into `directory` (which must exist)."""
+        _check(lib().dfk_closer_write(self._ctx, None if directory is None else str(directory).encode()))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
