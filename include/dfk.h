@@ -480,6 +480,61 @@ int dfk_closer_fetch(dfk_ctx* ctx, uint64_t* edges, uint64_t edges_cap, uint64_t
                      uint64_t* anchor_first, int32_t* anchors, uint64_t anchors_cap, uint64_t* n_anchors, uint64_t* read_first, uint64_t* reads, uint64_t reads_cap, uint64_t* n_reads);
 int dfk_closer_write(dfk_ctx* ctx, const char* dir);
 
+/* ---- the fifth step of the patching stage: CloseGap2's search for unplaced partners (10X/Closomatic.cc:554-585) ----
+ * For every pair (e1, e2), es = {e1, inv[e2]}, and each side ei: the forward reads on e = es[ei] whose mate is not forward on
+ * e' = es[1 - ei]; every 32-mer of the mate's bases (the whole read, as the .fastb has it) looked up among the 32-mers of the
+ * anchors of e' (bod); the mate kept, at pos - l, where all hits agree on one position.  Element 2 * pi + ei is what the loop for
+ * ei of pair pi pushes onto locs[1 - ei], in push order.  The rule, the packing of a 32-mer, the plan and the file's layout are
+ * stated in csrc/dfk_partners.h.  No qualities are read and no stack is built.
+ *   dfk_partners_build  needs the context's dfk_closer_build result, made for the same pairs: DFK_E_STATE without one, DFK_E_ARG for a
+ *                       pair whose closer edges are not in ce.  pairs NULL: the context's own dfk_hops_build* result.  The reads as
+ *                       dfk_paths_verify takes them, on the host (the kept reads have gone back to the arena by then); base_off NULL:
+ *                       dense.  Only the bases of the reads that are searched cross to the device, a batch of queries at a time.
+ *                       n_reads that is not the paths' n_reads, a null argument: DFK_E_ARG; an offset table that is not monotone or
+ *                       leaves a read fewer bytes than its bases need: DFK_E_INPUT.
+ *   dfk_partners_build_arrays  the same stage on host arrays, for tests that choose everything: inv; the edges' bases (packed,
+ *                       edge_off[n_edges + 1] in bytes, edge_len in bases); ce, loc_first, locs, anchor_first, anchors in
+ *                       dfk_closer_fetch's forms (in every rank the forward records first, ascending by id: DFK_E_ARG otherwise);
+ *                       pairs; reads; queries_per_batch (0 = what fits).  With dir the file is written there.  Its result is what
+ *                       dfk_partners_stats / _fetch / _write serve until the next dfk_partners_build*.
+ *   dfk_partners_stats  out[DFK_PARTNERS_WORDS]: the counters below
+ *   dfk_partners_fetch  starts ([n_elements + 1] words, or NULL; n_elements = 2 * n_pairs) and records (2 u64 a record,
+ *                       {id, pos | 1 << 32}).  A NULL buffer with cap 0 = the counts alone; a buffer too small: DFK_E_ARG
+ *   dfk_partners_write  into dir (which must exist), whole or not at all.  Little-endian, no byte undefined:
+ *                         a.close.partners  "DFKCPRT1" | u64 n = 2 * n_pairs | (n + 1) x u64 starts | 16-byte records
+ *                                           {i64 id, i32 pos, u32 fw = 1} -- the locs record
+ * The table of anchor 32-mers is built a range of ce ranks at a time (DFK_PIDX_RANGE_PAIRS forces small ranges, of the table and
+ * of the sides the queries are found in).  Every device block comes from the arena and is back when build returns.  Valid from
+ * dfk_closer_build until the paths are dropped, before or after dfk_paths_index_write; a later dfk_closer_build does not change a
+ * result already made.  A refused call changes nothing and an earlier result is still served.  Not for the ranks of a sharded run. */
+#define DFK_PARTNERS_WORDS 20
+#define DFK_PARTNERS_PAIRS 0         /* pairs */
+#define DFK_PARTNERS_QUERIES 1       /* mates searched (:566 passed) */
+#define DFK_PARTNERS_POSITIONS 2     /* read positions looked at (:574) */
+#define DFK_PARTNERS_ENTRIES 3       /* table entries: one per anchor and position of its edge, before UniqueSort, each closer edge once */
+#define DFK_PARTNERS_ANY_HIT 4       /* queries with any hit, */
+#define DFK_PARTNERS_KEPT 5          /* with one position (kept: the records), */
+#define DFK_PARTNERS_MULTI 6         /* with several (dropped) */
+#define DFK_PARTNERS_BATCHES 7       /* batches of queries */
+#define DFK_PARTNERS_RANGES 8        /* ranges of ce ranks the table was built in */
+#define DFK_PARTNERS_US 9            /* microseconds: the build call, */
+#define DFK_PARTNERS_US_TABLE 10     /* the table (entries, sorts), */
+#define DFK_PARTNERS_US_QUERIES 11   /* the queries (uploads of the closer's tables, forward parts, flags, scans), */
+#define DFK_PARTNERS_US_SEARCH 12    /* the search and the compaction, */
+#define DFK_PARTNERS_US_COPY 13      /* the gather of the reads' bases on the host and the copies either way */
+#define DFK_PARTNERS_SUM 14          /* sum and xor over positions i of h(i, word) (k_digest_seq): the records as u64 words, two a record (salt 0xDDDD) */
+#define DFK_PARTNERS_XOR 15
+#define DFK_PARTNERS_SEARCHED 16     /* queries against an edge that has anchors: those whose reads' bases cross to the device */
+int dfk_partners_build(dfk_ctx* ctx, const int32_t* pairs /* 2 per pair, or NULL */, uint64_t n_pairs, const uint8_t* packed_bases, const uint64_t* base_off /* or NULL: dense */,
+                       const uint32_t* read_len, uint64_t n_reads);
+int dfk_partners_build_arrays(dfk_ctx* ctx, uint64_t n_edges, const int32_t* inv, const uint8_t* edge_packed, const uint64_t* edge_off /* [n_edges + 1] */, const uint32_t* edge_len,
+                              uint64_t n_ce, const uint64_t* ce, const uint64_t* loc_first, const uint64_t* locs, const uint64_t* anchor_first, const int32_t* anchors,
+                              const int32_t* pairs, uint64_t n_pairs, const uint8_t* packed_bases, const uint64_t* base_off /* or NULL: dense */, const uint32_t* read_len, uint64_t n_reads,
+                              uint64_t queries_per_batch, const char* dir /* NULL = no file */);
+int dfk_partners_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_PARTNERS_WORDS] */);
+int dfk_partners_fetch(dfk_ctx* ctx, uint64_t* starts, uint64_t* n_elements, uint64_t* recs, uint64_t recs_cap, uint64_t* n_recs);
+int dfk_partners_write(dfk_ctx* ctx, const char* dir);
+
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).
  * dfk_paths_digest  fills out[DFK_CHECK_WORDS] with digests that depend on the CONTENT of a.paths, a.paths.inv, a.countsb and

@@ -552,7 +552,7 @@ int main(int argc, char** argv)
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
         {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
-        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -581,6 +581,10 @@ int main(int argc, char** argv)
 
     // CLOSER=True (the gap closers' read sets per edge, a.<K>/a.close.*) works from FindEdgePairs' pairs, the paths and a.dup
     if (truthy(a["CLOSER"]) && (!truthy(a["HOPS"]) || !truthy(a["PATHS"]))) give_up("CLOSER=True needs HOPS=True and PATHS=True: the closers' read sets are built per edge of the edge pairs, from the paths");
+
+    // PARTNERS=True (CloseGap2's unplaced partners, a.<K>/a.close.partners) works from the closers' read sets and the reads' bases
+    if (truthy(a["PARTNERS"]) && !truthy(a["CLOSER"])) give_up("PARTNERS=True needs CLOSER=True: the partners are searched for among the anchors of the closers' read sets");
+    const bool want_partners = truthy(a["PARTNERS"]);
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -934,7 +938,7 @@ int main(int argc, char** argv)
             // of one thread's page-table work -- at exit, if not before.  Behind the tasks that still read the maps.
             auto earlier = std::make_shared<std::vector<std::thread>>(std::move(background));
             background.clear();
-            background.emplace_back([&ins, earlier] { for (auto& x : *earlier) x.join(); for (In& x : ins) { x.fb.m.unmap(); x.qp.m.unmap(); } });
+            background.emplace_back([&ins, earlier, want_partners] { for (auto& x : *earlier) x.join(); for (In& x : ins) { if (!want_partners) x.fb.m.unmap(); x.qp.m.unmap(); } });      // (PARTNERS=True reads the bases of some reads again)
         }
         mark("count joined");
         t0 = now_s();
@@ -1041,6 +1045,17 @@ int main(int argc, char** argv)
                                (unsigned long long)cs[DFK_CLOSER_RANGES], (unsigned long long)cs[DFK_CLOSER_EDGES_SUM], (unsigned long long)cs[DFK_CLOSER_EDGES_XOR], (unsigned long long)cs[DFK_CLOSER_LOCS_SUM],
                                (unsigned long long)cs[DFK_CLOSER_LOCS_XOR], (unsigned long long)cs[DFK_CLOSER_ANCHORS_SUM], (unsigned long long)cs[DFK_CLOSER_ANCHORS_XOR], (unsigned long long)cs[DFK_CLOSER_READS_SUM],
                                (unsigned long long)cs[DFK_CLOSER_READS_XOR]);
+                        if (want_partners) {                                    // CloseGap2's unplaced partners (Closomatic.cc:554-585): a.<K>/a.close.partners, after a.close.*
+                            uint64_t ps[DFK_PARTNERS_WORDS] = {};
+                            const int prc = fast ? dfk_partners_build(ctx, nullptr, 0, h_packed + (n_reads ? ld64(h_boff) : 0), nullptr, (const uint32_t*)h_len, n_reads)      // (dense: validated at load)
+                                                 : dfk_partners_build(ctx, nullptr, 0, h_packed, (const uint64_t*)h_boff, (const uint32_t*)h_len, n_reads);
+                            if (prc || dfk_partners_write(ctx, dir.c_str()) || dfk_partners_stats(ctx, ps)) throw std::runtime_error(dfk_last_error());
+                            printf("DF_PARTNERS {\"pairs\": %llu, \"queries\": %llu, \"kept\": %llu, \"dropped_multi\": %llu, \"a.close.partners\": \"%016llx%016llx\", \"positions\": %llu, "
+                                   "\"entries\": %llu, \"batches\": %llu, \"ranges\": %llu}\n",
+                                   (unsigned long long)ps[DFK_PARTNERS_PAIRS], (unsigned long long)ps[DFK_PARTNERS_QUERIES], (unsigned long long)ps[DFK_PARTNERS_KEPT], (unsigned long long)ps[DFK_PARTNERS_MULTI],
+                                   (unsigned long long)ps[DFK_PARTNERS_SUM], (unsigned long long)ps[DFK_PARTNERS_XOR], (unsigned long long)ps[DFK_PARTNERS_POSITIONS], (unsigned long long)ps[DFK_PARTNERS_ENTRIES],
+                                   (unsigned long long)ps[DFK_PARTNERS_BATCHES], (unsigned long long)ps[DFK_PARTNERS_RANGES]);
+                        }
                     }
                 }
             }

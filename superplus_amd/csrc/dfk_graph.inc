@@ -43,12 +43,15 @@ struct HostGraph {
     void (*subset_free)(struct SubsetResult*) = nullptr;
     struct CloserResult* closer_arrays = nullptr;                    // dfk_closer_build_arrays' result (dfk_closer.inc)
     void (*closer_free)(struct CloserResult*) = nullptr;
+    struct PartnersResult* partners_arrays = nullptr;                // dfk_partners_build_arrays' result (dfk_partners.inc)
+    void (*partners_free)(struct PartnersResult*) = nullptr;
     ~HostGraph()
     {
         if (paths && paths_free) paths_free(paths);
         if (hops_arrays && paths_free) paths_free(hops_arrays);
         if (subset_arrays && subset_free) subset_free(subset_arrays);
         if (closer_arrays && closer_free) closer_free(closer_arrays);
+        if (partners_arrays && partners_free) partners_free(partners_arrays);
     }
 };
 

@@ -28,7 +28,7 @@ struct PathState {
     dfk_ctx* c = nullptr;
     std::string sink_path;                             // asked for by dfk_paths_sink, for the next build
     PathSink* sink = nullptr;                          // the one at work (or done, waiting for dfk_paths_write)
-    ~PathState() { sink_abort(this); if (shard && shard_free) shard_free(shard); if (sub && sub_free) sub_free(sub); if (closer && closer_free) closer_free(closer); }
+    ~PathState() { sink_abort(this); if (shard && shard_free) shard_free(shard); if (sub && sub_free) sub_free(sub); if (closer && closer_free) closer_free(closer); if (partners && partners_free) partners_free(partners); }
     DevBuf xlat, he_ce, he_left, he_right, from_start, from_vtx, from_edge, to_start, to_vtx, to_edge;
     bool tables = false;
     std::vector<PathBatch> batches;
@@ -41,6 +41,8 @@ struct PathState {
     void (*sub_free)(struct SubsetResult*) = nullptr;
     struct CloserResult* closer = nullptr;            // the closers' read sets per edge (dfk_closer_build, dfk_closer.inc): host memory
     void (*closer_free)(struct CloserResult*) = nullptr;
+    struct PartnersResult* partners = nullptr;        // the closers' unplaced partners (dfk_partners_build, dfk_partners.inc): host memory
+    void (*partners_free)(struct PartnersResult*) = nullptr;
     uint64_t ck[DFK_CHECK_WORDS] = {};                // dfk_paths_digest: what the steps so far have left (ck[DFK_CK_VALID]: which)
     int64_t read_id0 = 0;                             // a rank of a sharded run: the whole set's number of its first read (dfk_paths_shard.inc)
     void* shard = nullptr; void (*shard_free)(void*) = nullptr;
@@ -60,6 +62,8 @@ void paths_drop_results(dfk_ctx* c, PathState* P)
     P->sub = nullptr;
     if (P->closer && P->closer_free) P->closer_free(P->closer);
     P->closer = nullptr;
+    if (P->partners && P->partners_free) P->partners_free(P->partners);
+    P->partners = nullptr;
     for (uint64_t& w : P->ck) w = 0;
 }
 

@@ -34,6 +34,7 @@ EXPORTS = [
     "dfk_hops_build", "dfk_hops_build_bci", "dfk_hops_build_arrays", "dfk_hops_stats", "dfk_hops_fetch", "dfk_hops_write",
     "dfk_subset_build", "dfk_subset_build_arrays", "dfk_subset_stats", "dfk_subset_fetch", "dfk_subset_write",
     "dfk_closer_build", "dfk_closer_build_arrays", "dfk_closer_stats", "dfk_closer_fetch", "dfk_closer_write",
+    "dfk_partners_build", "dfk_partners_build_arrays", "dfk_partners_stats", "dfk_partners_fetch", "dfk_partners_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -54,6 +55,10 @@ CLOSER_WORDS = 24
 CLOSER = ["edges", "locs", "anchors", "reads", "prec", "mates_in", "mates_out", "dup_skipped", "ranges", "us", "us_mark", "us_weigh", "us_sweep", "us_sort",
           "edges_sum", "edges_xor", "locs_sum", "locs_xor", "anchors_sum", "anchors_xor", "reads_sum", "reads_xor"]
 CLOSER_FILES = ("a.close.edges", "a.close.locs", "a.close.anchors", "a.close.reads")
+# dfk_partners_stats' words (include/dfk.h, DFK_PARTNERS_*)
+PARTNERS_WORDS = 20
+PARTNERS = ["pairs", "queries", "positions", "entries", "any_hit", "kept", "multi", "batches", "ranges", "us", "us_table", "us_queries", "us_search", "us_copy", "sum", "xor", "searched"]
+PARTNERS_FILE = "a.close.partners"
 # dfk_adj_outcome's codes (include/dfk.h, DFK_ADJ_*)
 ADJ_OUTCOMES = ["not applicable", "used", "discarded: guess too low", "discarded: list problem", "no block", "dropped for an allocation",
                 "switched off"]
@@ -448,6 +453,57 @@ class Dfk:
     def closer_write(self, directory):
         """dfk_closer_write: a.close.edges, a.close.locs, a.close.anchors, a.close.reads into `directory` (which must exist)."""
         _check(lib().dfk_closer_write(self._ctx, None if directory is None else str(directory).encode()))
+
+    def partners_build(self, packed, base_off, read_len, pairs=None):
+        """dfk_partners_build: CloseGap2's unplaced partners per pair and side, after closer_build for the same pairs.  The reads as
+        paths_verify takes them (base_off None = dense); pairs None = the context's own hops result.  Returns partners_stats()."""
+        packed = None if packed is None else np.ascontiguousarray(packed, np.uint8)
+        base_off = None if base_off is None else np.ascontiguousarray(base_off, np.uint64)
+        read_len = None if read_len is None else np.ascontiguousarray(read_len, np.uint32)
+        n = 0 if read_len is None else len(read_len)
+        if pairs is None:
+            _check(lib().dfk_partners_build(self._ctx, None, C.c_uint64(0), _p(packed), _p(base_off), _p(read_len), C.c_uint64(n)))
+        else:
+            pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+            room = pairs if len(pairs) else np.zeros((1, 2), np.int32)      # (an empty list is still a list: NULL would mean the hops result)
+            _check(lib().dfk_partners_build(self._ctx, _p(room), C.c_uint64(len(pairs)), _p(packed), _p(base_off), _p(read_len), C.c_uint64(n)))
+        return self.partners_stats()
+
+    def partners_build_arrays(self, a, queries_per_batch=0, directory=None, **change):
+        """dfk_partners_build_arrays: the same stage on arrays.  a: dict(inv int32[E], edge_packed uint8[], edge_off uint64[E + 1],
+        edge_len uint32[E], ce uint64[n], loc_first uint64[n + 1], locs uint64[2 m], anchor_first uint64[n + 1], anchors int32[3 a],
+        pairs int32[p, 2], read_packed uint8[], read_off uint64[N + 1] or None (dense), read_len uint32[N]); with a directory
+        a.close.partners is written there.  Returns partners_stats()."""
+        a = dict(a); a.update(change)
+        kinds = dict(inv=np.int32, edge_packed=np.uint8, edge_off=np.uint64, edge_len=np.uint32, ce=np.uint64, loc_first=np.uint64, locs=np.uint64,
+                     anchor_first=np.uint64, anchors=np.int32, pairs=np.int32, read_packed=np.uint8, read_off=np.uint64, read_len=np.uint32)
+        n = {k: (0 if a[k] is None else len(a[k])) for k in kinds}
+        # (an empty array still has an address: NULL is for what is left out on purpose)
+        v = {k: None if a[k] is None else np.ascontiguousarray(a[k] if len(a[k]) else np.zeros(1, t), t) for k, t in kinds.items()}
+        _check(lib().dfk_partners_build_arrays(self._ctx, C.c_uint64(n["inv"]), _p(v["inv"]), _p(v["edge_packed"]), _p(v["edge_off"]), _p(v["edge_len"]), C.c_uint64(n["ce"]),
+                                               _p(v["ce"]), _p(v["loc_first"]), _p(v["locs"]), _p(v["anchor_first"]), _p(v["anchors"]), _p(v["pairs"]), C.c_uint64(n["pairs"]),
+                                               _p(v["read_packed"]), _p(v["read_off"]), _p(v["read_len"]), C.c_uint64(n["read_len"]), C.c_uint64(queries_per_batch),
+                                               None if directory is None else str(directory).encode()))
+        return self.partners_stats()
+
+    def partners_stats(self):
+        """dfk_partners_stats: {counter: value} -- pairs, queries, read positions, table entries, queries with a hit, kept, dropped,
+        batches, ranges, times, digest."""
+        out = (C.c_uint64 * PARTNERS_WORDS)()
+        _check(lib().dfk_partners_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(PARTNERS)}
+
+    def partners_fetch(self):
+        """dfk_partners_fetch: dict(starts uint64[2 p + 1], recs uint64[m, 2] (id, pos | 1 << 32))."""
+        ne, nr = C.c_uint64(), C.c_uint64()
+        _check(lib().dfk_partners_fetch(self._ctx, None, C.byref(ne), None, C.c_uint64(0), C.byref(nr)))
+        starts, recs = np.zeros(ne.value + 1, np.uint64), np.zeros((nr.value, 2), np.uint64)
+        _check(lib().dfk_partners_fetch(self._ctx, _p(starts), C.byref(ne), _p(recs), C.c_uint64(nr.value), C.byref(nr)))
+        return dict(starts=starts, recs=recs)
+
+    def partners_write(self, directory):
+        """dfk_partners_write: a.close.partners into `directory` (which must exist)."""
+        _check(lib().dfk_partners_write(self._ctx, None if directory is None else str(directory).encode()))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
