@@ -535,6 +535,67 @@ int dfk_partners_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_PARTNERS_WORDS] */);
 int dfk_partners_fetch(dfk_ctx* ctx, uint64_t* starts, uint64_t* n_elements, uint64_t* recs, uint64_t recs_cap, uint64_t* n_recs);
 int dfk_partners_write(dfk_ctx* ctx, const char* dir);
 
+/* ---- the sixth step of the patching stage: CloseGap2's read stacks and their column consensus (10X/Closomatic.cc:587-640) ----
+ * For every pair (e1, e2), es = {e1, inv[e2]}, and each side ei: the readstack of locs(e) and the partners pushed onto it, M columns
+ * wide, trimmed to its last 400 columns where it is wider, reversed where e == inv[e2] (ReadStack.cc:714-725, 346-353), and the
+ * column consensus GetOffsets1 takes of it first (ReadStack.cc:1219-1223, 400-404, 1841-1861): per column the rows in row order, a
+ * defined cell adding 0.1 for Q0, 0.2 for Q1 and Q2 and q otherwise to its base's double, the first maximum.  NO STACK IS STORED:
+ * what is kept per pair and side is the consensus (at most 400 bases) and the stack's dimensions.  Element 2 * pi + ei is stacks[ei]
+ * of pair pi.  The rule, the cell, the plan and the file's layout are stated in csrc/dfk_cons.h.
+ *   dfk_cons_build      needs the context's dfk_closer_build AND dfk_partners_build results, made for the same pairs: DFK_E_STATE
+ *                       without either; DFK_E_ARG for pairs that are not those the partners were made for.  pairs NULL: the
+ *                       context's own dfk_hops_build* result.  The reads with their PQVec qualities as dfk_paths_build takes them, on
+ *                       the host; base_off NULL: dense.  Only the reads that rows inside a stack's window name cross to the device,
+ *                       each once per batch of stacks, and are decoded there.  n_reads that is not the paths' n_reads, a null
+ *                       argument: DFK_E_ARG; an offset table (bases or qualities) that is not monotone or leaves a read fewer bytes
+ *                       than its bases need, a PQVec stream that does not hold exactly read_len values: DFK_E_INPUT.
+ *   dfk_cons_build_arrays  the same stage on host arrays, for tests that choose everything: inv and kmers per edge (K is the
+ *                       context's); ce, loc_first, locs in dfk_closer_fetch's forms; the partners' starts ([2 * n_pairs + 1]) and
+ *                       records in dfk_partners_fetch's forms; pairs; reads and qualities; stacks_per_batch (0 = what fits).  With
+ *                       dir the file is written there.  Its result is what dfk_cons_stats / _fetch / _write serve until the next
+ *                       dfk_cons_build*.
+ *   dfk_cons_stats      out[DFK_CONS_WORDS]: the counters below
+ *   dfk_cons_fetch      starts ([n_elements + 1] words, or NULL; n_elements = 2 * n_pairs), dims (4 u32 an element: rows,
+ *                       rows_kept, M, cols; or NULL) and the bases, a byte each.  A NULL buffer with cap 0 = the counts alone; a
+ *                       buffer too small: DFK_E_ARG
+ *   dfk_cons_write      into dir (which must exist), whole or not at all.  Little-endian, no byte undefined:
+ *                         a.close.cons  "DFKCCON1" | u64 n = 2 * n_pairs | (n + 1) x u64 starts, in bases | n x 16-byte dims
+ *                                       {u32 rows, u32 rows_kept, i32 M, u32 cols} | the bases, a byte each (0..3) | zero bytes to
+ *                                       a multiple of 8.  starts[k + 1] - starts[k] == cols[k]
+ * Dimensions and live rows are found a range of stacks at a time (DFK_PIDX_RANGE_PAIRS forces small ranges, in rows).  Every device
+ * block comes from the arena and is back when build returns.  The result stays in host memory with the paths until the next build or
+ * until the paths are dropped.  A refused call changes nothing and an earlier result is still served.  Not for the ranks of a
+ * sharded run. */
+#define DFK_CONS_WORDS 24
+#define DFK_CONS_PAIRS 0             /* pairs */
+#define DFK_CONS_STACKS 1            /* stacks: two a pair */
+#define DFK_CONS_ROWS 2              /* rows of all stacks (:599), */
+#define DFK_CONS_LIVE 3              /* those whose span meets their stack's kept columns: the rows the device walks, */
+#define DFK_CONS_ROWS_KEPT 4         /* the rows the stacks have after Trim */
+#define DFK_CONS_TRIMMED 5           /* stacks wider than 400 columns */
+#define DFK_CONS_REVERSED 6          /* stacks reversed (e == inv[e2]) */
+#define DFK_CONS_COLUMNS 7           /* columns of all stacks after Trim: the bases of the result */
+#define DFK_CONS_CELLS 8             /* defined cells added to a column's sums */
+#define DFK_CONS_DECODED 9           /* reads sent up and decoded, summed over the batches */
+#define DFK_CONS_BATCHES 10          /* batches of stacks */
+#define DFK_CONS_RANGES 11           /* ranges of stacks the dimensions and live rows were found in */
+#define DFK_CONS_US 12               /* microseconds: the build call, */
+#define DFK_CONS_US_DIMS 13          /* the uploads of the tables and lengths, dimensions and live rows, */
+#define DFK_CONS_US_COPY 14          /* the gather of the reads on the host and the copies either way, */
+#define DFK_CONS_US_DECODE 15        /* the decode, */
+#define DFK_CONS_US_CONS 16          /* the consensus */
+#define DFK_CONS_SUM 17              /* sum and xor over positions i of h(i, value) (k_digest_seq, salt 0xEEEE): the dims as u32 words, then the bases one value each */
+#define DFK_CONS_XOR 18
+int dfk_cons_build(dfk_ctx* ctx, const int32_t* pairs /* 2 per pair, or NULL */, uint64_t n_pairs, const uint8_t* packed_bases, const uint64_t* base_off /* or NULL: dense */,
+                   const uint32_t* read_len, const uint8_t* pq, const uint64_t* pq_off, uint64_t n_reads);
+int dfk_cons_build_arrays(dfk_ctx* ctx, uint64_t n_edges, const int32_t* inv, const int32_t* kmers, uint64_t n_ce, const uint64_t* ce, const uint64_t* loc_first, const uint64_t* locs,
+                          const uint64_t* part_first /* [2 * n_pairs + 1] */, const uint64_t* parts, const int32_t* pairs, uint64_t n_pairs,
+                          const uint8_t* packed_bases, const uint64_t* base_off /* or NULL: dense */, const uint32_t* read_len, const uint8_t* pq, const uint64_t* pq_off, uint64_t n_reads,
+                          uint64_t stacks_per_batch, const char* dir /* NULL = no file */);
+int dfk_cons_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_CONS_WORDS] */);
+int dfk_cons_fetch(dfk_ctx* ctx, uint64_t* starts, uint32_t* dims, uint64_t* n_elements, uint8_t* bases, uint64_t bases_cap, uint64_t* n_bases);
+int dfk_cons_write(dfk_ctx* ctx, const char* dir);
+
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).
  * dfk_paths_digest  fills out[DFK_CHECK_WORDS] with digests that depend on the CONTENT of a.paths, a.paths.inv, a.countsb and

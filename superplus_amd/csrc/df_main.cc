@@ -552,7 +552,7 @@ int main(int argc, char** argv)
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
         {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
-        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -585,6 +585,11 @@ int main(int argc, char** argv)
     // PARTNERS=True (CloseGap2's unplaced partners, a.<K>/a.close.partners) works from the closers' read sets and the reads' bases
     if (truthy(a["PARTNERS"]) && !truthy(a["CLOSER"])) give_up("PARTNERS=True needs CLOSER=True: the partners are searched for among the anchors of the closers' read sets");
     const bool want_partners = truthy(a["PARTNERS"]);
+
+    // CONS=True (CloseGap2's stack consensus per pair and side, a.<K>/a.close.cons) works from the closers' locs, the partners and the reads
+    // with their qualities
+    if (truthy(a["CONS"]) && !want_partners) give_up("CONS=True needs PARTNERS=True: a stack's rows are the closers' locs and the partners pushed onto them");
+    const bool want_cons = truthy(a["CONS"]);
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -938,7 +943,7 @@ int main(int argc, char** argv)
             // of one thread's page-table work -- at exit, if not before.  Behind the tasks that still read the maps.
             auto earlier = std::make_shared<std::vector<std::thread>>(std::move(background));
             background.clear();
-            background.emplace_back([&ins, earlier, want_partners] { for (auto& x : *earlier) x.join(); for (In& x : ins) { if (!want_partners) x.fb.m.unmap(); x.qp.m.unmap(); } });      // (PARTNERS=True reads the bases of some reads again)
+            background.emplace_back([&ins, earlier, want_partners, want_cons] { for (auto& x : *earlier) x.join(); for (In& x : ins) { if (!want_partners) x.fb.m.unmap(); if (!want_cons) x.qp.m.unmap(); } });      // (PARTNERS=True reads the bases of some reads again, CONS=True their qualities too)
         }
         mark("count joined");
         t0 = now_s();
@@ -1055,6 +1060,18 @@ int main(int argc, char** argv)
                                    (unsigned long long)ps[DFK_PARTNERS_PAIRS], (unsigned long long)ps[DFK_PARTNERS_QUERIES], (unsigned long long)ps[DFK_PARTNERS_KEPT], (unsigned long long)ps[DFK_PARTNERS_MULTI],
                                    (unsigned long long)ps[DFK_PARTNERS_SUM], (unsigned long long)ps[DFK_PARTNERS_XOR], (unsigned long long)ps[DFK_PARTNERS_POSITIONS], (unsigned long long)ps[DFK_PARTNERS_ENTRIES],
                                    (unsigned long long)ps[DFK_PARTNERS_BATCHES], (unsigned long long)ps[DFK_PARTNERS_RANGES]);
+                        }
+                        if (want_cons) {                                        // CloseGap2's stack consensus (Closomatic.cc:587-640): a.<K>/a.close.cons, after a.close.partners
+                            uint64_t ns[DFK_CONS_WORDS] = {};
+                            const int nrc = fast ? dfk_cons_build(ctx, nullptr, 0, h_packed + (n_reads ? ld64(h_boff) : 0), nullptr, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, n_reads)      // (dense: validated at load)
+                                                 : dfk_cons_build(ctx, nullptr, 0, h_packed, (const uint64_t*)h_boff, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, n_reads);
+                            if (nrc || dfk_cons_write(ctx, dir.c_str()) || dfk_cons_stats(ctx, ns)) throw std::runtime_error(dfk_last_error());
+                            printf("DF_CONS {\"pairs\": %llu, \"stacks\": %llu, \"trimmed\": %llu, \"rows_kept\": %llu, \"columns\": %llu, \"a.close.cons\": \"%016llx%016llx\", \"rows\": %llu, "
+                                   "\"live_rows\": %llu, \"reversed\": %llu, \"cells\": %llu, \"batches\": %llu, \"ranges\": %llu}\n",
+                                   (unsigned long long)ns[DFK_CONS_PAIRS], (unsigned long long)ns[DFK_CONS_STACKS], (unsigned long long)ns[DFK_CONS_TRIMMED], (unsigned long long)ns[DFK_CONS_ROWS_KEPT],
+                                   (unsigned long long)ns[DFK_CONS_COLUMNS], (unsigned long long)ns[DFK_CONS_SUM], (unsigned long long)ns[DFK_CONS_XOR], (unsigned long long)ns[DFK_CONS_ROWS],
+                                   (unsigned long long)ns[DFK_CONS_LIVE], (unsigned long long)ns[DFK_CONS_REVERSED], (unsigned long long)ns[DFK_CONS_CELLS], (unsigned long long)ns[DFK_CONS_BATCHES],
+                                   (unsigned long long)ns[DFK_CONS_RANGES]);
                         }
                     }
                 }

@@ -2281,5 +2281,6 @@ int dfk_adj_outcome(dfk_ctx* c, uint32_t* outcome, uint64_t* slots)
 #include "dfk_subset.inc"
 #include "dfk_closer.inc"
 #include "dfk_partners.inc"
+#include "dfk_cons.inc"
 #include "dfk_paths_shard.inc"
 #include "dfk_pbf.inc"

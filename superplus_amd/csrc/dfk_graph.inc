@@ -45,6 +45,8 @@ struct HostGraph {
     void (*closer_free)(struct CloserResult*) = nullptr;
     struct PartnersResult* partners_arrays = nullptr;                // dfk_partners_build_arrays' result (dfk_partners.inc)
     void (*partners_free)(struct PartnersResult*) = nullptr;
+    struct ConsResult* cons_arrays = nullptr;                        // dfk_cons_build_arrays' result (dfk_cons.inc)
+    void (*cons_free)(struct ConsResult*) = nullptr;
     ~HostGraph()
     {
         if (paths && paths_free) paths_free(paths);
@@ -52,6 +54,7 @@ struct HostGraph {
         if (subset_arrays && subset_free) subset_free(subset_arrays);
         if (closer_arrays && closer_free) closer_free(closer_arrays);
         if (partners_arrays && partners_free) partners_free(partners_arrays);
+        if (cons_arrays && cons_free) cons_free(cons_arrays);
     }
 };
 

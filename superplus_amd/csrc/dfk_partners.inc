@@ -18,6 +18,7 @@ namespace {
 struct PartnersResult {
     std::vector<uint64_t> starts;                 // [2 * n_pairs + 1]
     std::vector<uint64_t> recs;                   // two words a record: id, pos | 1 << 32
+    std::vector<int32_t> pairs;                   // the pairs it was made for (dfk_cons_build takes no others)
     uint64_t stats[DFK_PARTNERS_WORDS] = {};
 };
 void partners_result_free(PartnersResult* r) { delete r; }
@@ -268,7 +269,7 @@ int partners_build(dfk_ctx* c, const PartnersSource& S, const int32_t* pairs, ui
             k0 = k1;
         }
         // ---- the records in query order, the starts per side, the digest
-        R->starts.assign(n_sides + 1, 0);
+        R->starts.assign(n_sides + 1, 0); R->pairs.assign(pairs, pairs + 2 * n_pairs);
         for (uint64_t i = 0; i < n_q; ++i) {
             if (!q_kept[i]) continue;
             R->recs.push_back(q_id[i]); R->recs.push_back(dfk_closer::loc_word1(q_pos[i], true));

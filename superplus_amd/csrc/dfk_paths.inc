@@ -28,7 +28,7 @@ struct PathState {
     dfk_ctx* c = nullptr;
     std::string sink_path;                             // asked for by dfk_paths_sink, for the next build
     PathSink* sink = nullptr;                          // the one at work (or done, waiting for dfk_paths_write)
-    ~PathState() { sink_abort(this); if (shard && shard_free) shard_free(shard); if (sub && sub_free) sub_free(sub); if (closer && closer_free) closer_free(closer); if (partners && partners_free) partners_free(partners); }
+    ~PathState() { sink_abort(this); if (shard && shard_free) shard_free(shard); if (sub && sub_free) sub_free(sub); if (closer && closer_free) closer_free(closer); if (partners && partners_free) partners_free(partners); if (cons && cons_free) cons_free(cons); }
     DevBuf xlat, he_ce, he_left, he_right, from_start, from_vtx, from_edge, to_start, to_vtx, to_edge;
     bool tables = false;
     std::vector<PathBatch> batches;
@@ -43,6 +43,8 @@ struct PathState {
     void (*closer_free)(struct CloserResult*) = nullptr;
     struct PartnersResult* partners = nullptr;        // the closers' unplaced partners (dfk_partners_build, dfk_partners.inc): host memory
     void (*partners_free)(struct PartnersResult*) = nullptr;
+    struct ConsResult* cons = nullptr;                // the stacks' consensus per pair and side (dfk_cons_build, dfk_cons.inc): host memory
+    void (*cons_free)(struct ConsResult*) = nullptr;
     uint64_t ck[DFK_CHECK_WORDS] = {};                // dfk_paths_digest: what the steps so far have left (ck[DFK_CK_VALID]: which)
     int64_t read_id0 = 0;                             // a rank of a sharded run: the whole set's number of its first read (dfk_paths_shard.inc)
     void* shard = nullptr; void (*shard_free)(void*) = nullptr;
@@ -64,6 +66,8 @@ void paths_drop_results(dfk_ctx* c, PathState* P)
     P->closer = nullptr;
     if (P->partners && P->partners_free) P->partners_free(P->partners);
     P->partners = nullptr;
+    if (P->cons && P->cons_free) P->cons_free(P->cons);
+    P->cons = nullptr;
     for (uint64_t& w : P->ck) w = 0;
 }
 

@@ -35,6 +35,7 @@ EXPORTS = [
     "dfk_subset_build", "dfk_subset_build_arrays", "dfk_subset_stats", "dfk_subset_fetch", "dfk_subset_write",
     "dfk_closer_build", "dfk_closer_build_arrays", "dfk_closer_stats", "dfk_closer_fetch", "dfk_closer_write",
     "dfk_partners_build", "dfk_partners_build_arrays", "dfk_partners_stats", "dfk_partners_fetch", "dfk_partners_write",
+    "dfk_cons_build", "dfk_cons_build_arrays", "dfk_cons_stats", "dfk_cons_fetch", "dfk_cons_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -59,6 +60,11 @@ CLOSER_FILES = ("a.close.edges", "a.close.locs", "a.close.anchors", "a.close.rea
 PARTNERS_WORDS = 20
 PARTNERS = ["pairs", "queries", "positions", "entries", "any_hit", "kept", "multi", "batches", "ranges", "us", "us_table", "us_queries", "us_search", "us_copy", "sum", "xor", "searched"]
 PARTNERS_FILE = "a.close.partners"
+# dfk_cons_stats' words (include/dfk.h, DFK_CONS_*)
+CONS_WORDS = 24
+CONS = ["pairs", "stacks", "rows", "live", "rows_kept", "trimmed", "reversed", "columns", "cells", "decoded", "batches", "ranges", "us", "us_dims", "us_copy", "us_decode", "us_cons",
+        "sum", "xor"]
+CONS_FILE = "a.close.cons"
 # dfk_adj_outcome's codes (include/dfk.h, DFK_ADJ_*)
 ADJ_OUTCOMES = ["not applicable", "used", "discarded: guess too low", "discarded: list problem", "no block", "dropped for an allocation",
                 "switched off"]
@@ -504,6 +510,61 @@ class Dfk:
     def partners_write(self, directory):
         """dfk_partners_write: a.close.partners into `directory` (which must exist)."""
         _check(lib().dfk_partners_write(self._ctx, None if directory is None else str(directory).encode()))
+
+    def cons_build(self, packed, base_off, read_len, pq_bytes, pq_off, pairs=None):
+        """dfk_cons_build: CloseGap2's stack consensus per pair and side, after closer_build and partners_build for the same pairs.  The
+        reads and their PQVec qualities as paths_build takes them (base_off None = dense); pairs None = the context's own hops result.
+        Returns cons_stats()."""
+        packed = None if packed is None else np.ascontiguousarray(packed, np.uint8)
+        base_off = None if base_off is None else np.ascontiguousarray(base_off, np.uint64)
+        read_len = None if read_len is None else np.ascontiguousarray(read_len, np.uint32)
+        pq_bytes = None if pq_bytes is None else np.ascontiguousarray(pq_bytes, np.uint8)
+        pq_off = None if pq_off is None else np.ascontiguousarray(pq_off, np.uint64)
+        n = 0 if read_len is None else len(read_len)
+        if pairs is None:
+            _check(lib().dfk_cons_build(self._ctx, None, C.c_uint64(0), _p(packed), _p(base_off), _p(read_len), _p(pq_bytes), _p(pq_off), C.c_uint64(n)))
+        else:
+            pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+            room = pairs if len(pairs) else np.zeros((1, 2), np.int32)      # (an empty list is still a list: NULL would mean the hops result)
+            _check(lib().dfk_cons_build(self._ctx, _p(room), C.c_uint64(len(pairs)), _p(packed), _p(base_off), _p(read_len), _p(pq_bytes), _p(pq_off), C.c_uint64(n)))
+        return self.cons_stats()
+
+    def cons_build_arrays(self, a, stacks_per_batch=0, directory=None, **change):
+        """dfk_cons_build_arrays: the same stage on arrays.  a: dict(inv int32[E], kmers int32[E], ce uint64[n], loc_first uint64[n + 1],
+        locs uint64[2 m], part_first uint64[2 p + 1], parts uint64[2 r], pairs int32[p, 2], read_packed uint8[], read_off uint64[N + 1] or
+        None (dense), read_len uint32[N], pq uint8[], pq_off uint64[N + 1]); with a directory a.close.cons is written there.  Returns
+        cons_stats()."""
+        a = dict(a); a.update(change)
+        kinds = dict(inv=np.int32, kmers=np.int32, ce=np.uint64, loc_first=np.uint64, locs=np.uint64, part_first=np.uint64, parts=np.uint64, pairs=np.int32,
+                     read_packed=np.uint8, read_off=np.uint64, read_len=np.uint32, pq=np.uint8, pq_off=np.uint64)
+        n = {k: (0 if a[k] is None else len(a[k])) for k in kinds}
+        # (an empty array still has an address: NULL is for what is left out on purpose)
+        v = {k: None if a[k] is None else np.ascontiguousarray(a[k] if len(a[k]) else np.zeros(1, t), t) for k, t in kinds.items()}
+        _check(lib().dfk_cons_build_arrays(self._ctx, C.c_uint64(n["inv"]), _p(v["inv"]), _p(v["kmers"]), C.c_uint64(n["ce"]), _p(v["ce"]), _p(v["loc_first"]), _p(v["locs"]),
+                                           _p(v["part_first"]), _p(v["parts"]), _p(v["pairs"]), C.c_uint64(n["pairs"]), _p(v["read_packed"]), _p(v["read_off"]), _p(v["read_len"]),
+                                           _p(v["pq"]), _p(v["pq_off"]), C.c_uint64(n["read_len"]), C.c_uint64(stacks_per_batch), None if directory is None else str(directory).encode()))
+        return self.cons_stats()
+
+    def cons_stats(self):
+        """dfk_cons_stats: {counter: value} -- pairs, stacks, rows, live rows, rows kept, stacks trimmed and reversed, columns, cells added,
+        reads decoded, batches, ranges, times, digest."""
+        out = (C.c_uint64 * CONS_WORDS)()
+        _check(lib().dfk_cons_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(CONS)}
+
+    def cons_fetch(self):
+        """dfk_cons_fetch: dict(starts uint64[2 p + 1], dims int64[2 p, 4] (rows, rows_kept, M, cols), bases uint8[columns])."""
+        ne, nb = C.c_uint64(), C.c_uint64()
+        _check(lib().dfk_cons_fetch(self._ctx, None, None, C.byref(ne), None, C.c_uint64(0), C.byref(nb)))
+        starts, dims, bases = np.zeros(ne.value + 1, np.uint64), np.zeros((max(1, ne.value), 4), np.uint32), np.zeros(max(1, nb.value), np.uint8)
+        _check(lib().dfk_cons_fetch(self._ctx, _p(starts), _p(dims), C.byref(ne), _p(bases), C.c_uint64(nb.value), C.byref(nb)))
+        dims = dims[: ne.value].astype(np.int64)
+        dims[:, 2] = dims[:, 2].astype(np.uint32).view(np.int32) if len(dims) else dims[:, 2]
+        return dict(starts=starts, dims=dims, bases=bases[: nb.value])
+
+    def cons_write(self, directory):
+        """dfk_cons_write: a.close.cons into `directory` (which must exist)."""
+        _check(lib().dfk_cons_write(self._ctx, None if directory is None else str(directory).encode()))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
