@@ -596,6 +596,56 @@ int dfk_cons_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_CONS_WORDS] */);
 int dfk_cons_fetch(dfk_ctx* ctx, uint64_t* starts, uint32_t* dims, uint64_t* n_elements, uint8_t* bases, uint64_t bases_cap, uint64_t* n_bases);
 int dfk_cons_write(dfk_ctx* ctx, const char* dir);
 
+/* ---- the seventh step of the patching stage: CloseGap2's stack offsets per pair (GetOffsets1, paths/long/ReadStack.cc:1192-1512) ----
+ * The statement behind the stacks' consensus (10X/Closomatic.cc:648): the offsets at which a pair's two consensus sequences overlap
+ * convincingly -- the candidates from shared 8-mers, the bits test against a table of log binomial sums, invalidation, big near small.
+ * A pair gets a closure only with one or two surviving offsets (:651).  The result is a function of the two consensus sequences
+ * alone.  The rule, the table, the plan and the file's layout are stated in csrc/dfk_offsets.h.
+ *   dfk_offsets_build   works from the context's latest dfk_cons_build* result: DFK_E_STATE without one.
+ *   dfk_offsets_build_arrays  the same stage on host arrays, for tests that choose everything: element 2 * pi + ei is con(ei + 1) of
+ *                       pair pi, bases[starts[q] .. starts[q + 1]), a byte a base.  DFK_E_ARG for a null argument, starts that do not
+ *                       begin at 0 or fall, a base above 3, an element longer than 400.  pairs_per_batch 0 = what fits; with a dir
+ *                       the file is written there.
+ *   A refused call changes nothing: dfk_offsets_stats / _fetch / _write serve the latest result of either build until the next one.
+ *   dfk_offsets_stats   out[DFK_OFFSETS_WORDS]: the counters below
+ *   dfk_offsets_fetch   starts ([n_pairs + 1] words, in records, or NULL), words (4 u32 a pair: candidates, passed, survivors, 0, or
+ *                       NULL), the 32-byte records; NULL with cap 0 gives the counts alone; a buffer too small DFK_E_ARG, the counts
+ *                       still told.
+ *   dfk_offsets_write   into dir (which must exist), whole or not at all.  Little-endian, no byte undefined:
+ *                         a.close.offsets  "DFKCOFF1" | u64 n_pairs | (n_pairs + 1) x u64 starts, in records | n_pairs x 16-byte
+ *                                       { u32 candidates, u32 passed, u32 survivors, u32 0 } | 32-byte records { i32 offset,
+ *                                       i32 overlap, i32 fraglen, i32 mismatch, f64 bits, u32 state, u32 0 }: one per offset that
+ *                                       passed the bits test, ascending; state 0 surviving, 1 removed by invalidation, 2 removed as
+ *                                       small near big. */
+#define DFK_OFFSETS_WORDS 24
+#define DFK_OFFSETS_PAIRS 0          /* pairs */
+#define DFK_OFFSETS_CANDIDATES 1     /* candidate offsets (:1254), */
+#define DFK_OFFSETS_PASSED 2         /* those with bits >= 25.0 (:1328): the records, */
+#define DFK_OFFSETS_INVALIDATED 3    /* of them removed by another offset's validated positions (:1485), */
+#define DFK_OFFSETS_DELETED_SMALL 4  /* removed as small near big (:1502), */
+#define DFK_OFFSETS_SURVIVORS 5      /* returned */
+#define DFK_OFFSETS_PAIRS_0 6        /* pairs with no surviving offset, */
+#define DFK_OFFSETS_PAIRS_1 7        /* one, */
+#define DFK_OFFSETS_PAIRS_2 8        /* two, */
+#define DFK_OFFSETS_PAIRS_MORE 9     /* more */
+#define DFK_OFFSETS_CLOSABLE 10      /* pairs with one or two (Closomatic.cc:651) */
+#define DFK_OFFSETS_LOOKUPS 11       /* table cells read by the bits test (:1324) */
+#define DFK_OFFSETS_BATCHES 12       /* batches of pairs */
+#define DFK_OFFSETS_US 13            /* microseconds: the build call, */
+#define DFK_OFFSETS_US_CANDIDATES 14 /* the candidate kernels with their scan, */
+#define DFK_OFFSETS_US_BITS 15       /* the bits kernel, */
+#define DFK_OFFSETS_US_COMPACT 16    /* the scan and compaction of those that passed, */
+#define DFK_OFFSETS_US_TAIL 17       /* invalidation and big near small on the host, */
+#define DFK_OFFSETS_US_COPY 18       /* the uploads and the copies back */
+#define DFK_OFFSETS_SUM 19           /* sum and xor over positions i of h(i, value) (k_digest_seq, salt 0xF0F0): the per-pair words, then the records as u32 words */
+#define DFK_OFFSETS_XOR 20
+int dfk_offsets_build(dfk_ctx* ctx);
+int dfk_offsets_build_arrays(dfk_ctx* ctx, uint64_t n_pairs, const uint64_t* starts /* [2 * n_pairs + 1] */, const uint8_t* bases, uint64_t pairs_per_batch /* 0 = what fits */,
+                             const char* dir /* NULL = no file */);
+int dfk_offsets_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_OFFSETS_WORDS] */);
+int dfk_offsets_fetch(dfk_ctx* ctx, uint64_t* starts, uint32_t* words, uint64_t* n_pairs, void* records, uint64_t records_cap, uint64_t* n_records);
+int dfk_offsets_write(dfk_ctx* ctx, const char* dir);
+
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).
  * dfk_paths_digest  fills out[DFK_CHECK_WORDS] with digests that depend on the CONTENT of a.paths, a.paths.inv, a.countsb and

@@ -552,7 +552,7 @@ int main(int argc, char** argv)
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
         {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
-        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -590,6 +590,10 @@ int main(int argc, char** argv)
     // with their qualities
     if (truthy(a["CONS"]) && !want_partners) give_up("CONS=True needs PARTNERS=True: a stack's rows are the closers' locs and the partners pushed onto them");
     const bool want_cons = truthy(a["CONS"]);
+
+    // OFFSETS=True (CloseGap2's stack offsets per pair, GetOffsets1, a.<K>/a.close.offsets) works from the two consensus sequences of a pair
+    if (truthy(a["OFFSETS"]) && !want_cons) give_up("OFFSETS=True needs CONS=True: the offsets are found between the two stack consensus sequences of a pair");
+    const bool want_offsets = truthy(a["OFFSETS"]);
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -1072,6 +1076,17 @@ int main(int argc, char** argv)
                                    (unsigned long long)ns[DFK_CONS_COLUMNS], (unsigned long long)ns[DFK_CONS_SUM], (unsigned long long)ns[DFK_CONS_XOR], (unsigned long long)ns[DFK_CONS_ROWS],
                                    (unsigned long long)ns[DFK_CONS_LIVE], (unsigned long long)ns[DFK_CONS_REVERSED], (unsigned long long)ns[DFK_CONS_CELLS], (unsigned long long)ns[DFK_CONS_BATCHES],
                                    (unsigned long long)ns[DFK_CONS_RANGES]);
+                        }
+                        if (want_offsets) {                                     // GetOffsets1 per pair (Closomatic.cc:648): a.<K>/a.close.offsets, after a.close.cons
+                            uint64_t os[DFK_OFFSETS_WORDS] = {};
+                            if (dfk_offsets_build(ctx) || dfk_offsets_write(ctx, dir.c_str()) || dfk_offsets_stats(ctx, os)) throw std::runtime_error(dfk_last_error());
+                            printf("DF_OFFSETS {\"pairs\": %llu, \"candidates\": %llu, \"passed\": %llu, \"invalidated\": %llu, \"deleted_small\": %llu, \"survivors\": %llu, "
+                                   "\"a.close.offsets\": \"%016llx%016llx\", \"pairs_0\": %llu, \"pairs_1\": %llu, \"pairs_2\": %llu, \"pairs_more\": %llu, \"closable\": %llu, \"lookups\": %llu, "
+                                   "\"batches\": %llu}\n",
+                                   (unsigned long long)os[DFK_OFFSETS_PAIRS], (unsigned long long)os[DFK_OFFSETS_CANDIDATES], (unsigned long long)os[DFK_OFFSETS_PASSED], (unsigned long long)os[DFK_OFFSETS_INVALIDATED],
+                                   (unsigned long long)os[DFK_OFFSETS_DELETED_SMALL], (unsigned long long)os[DFK_OFFSETS_SURVIVORS], (unsigned long long)os[DFK_OFFSETS_SUM], (unsigned long long)os[DFK_OFFSETS_XOR],
+                                   (unsigned long long)os[DFK_OFFSETS_PAIRS_0], (unsigned long long)os[DFK_OFFSETS_PAIRS_1], (unsigned long long)os[DFK_OFFSETS_PAIRS_2], (unsigned long long)os[DFK_OFFSETS_PAIRS_MORE],
+                                   (unsigned long long)os[DFK_OFFSETS_CLOSABLE], (unsigned long long)os[DFK_OFFSETS_LOOKUPS], (unsigned long long)os[DFK_OFFSETS_BATCHES]);
                         }
                     }
                 }

@@ -47,6 +47,8 @@ struct HostGraph {
     void (*partners_free)(struct PartnersResult*) = nullptr;
     struct ConsResult* cons_arrays = nullptr;                        // dfk_cons_build_arrays' result (dfk_cons.inc)
     void (*cons_free)(struct ConsResult*) = nullptr;
+    struct OffsetsResult* offsets = nullptr;                         // the latest dfk_offsets_build*'s result (dfk_offsets.inc)
+    void (*offsets_free)(struct OffsetsResult*) = nullptr;
     ~HostGraph()
     {
         if (paths && paths_free) paths_free(paths);
@@ -55,6 +57,7 @@ struct HostGraph {
         if (closer_arrays && closer_free) closer_free(closer_arrays);
         if (partners_arrays && partners_free) partners_free(partners_arrays);
         if (cons_arrays && cons_free) cons_free(cons_arrays);
+        if (offsets && offsets_free) offsets_free(offsets);
     }
 };
 

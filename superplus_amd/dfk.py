@@ -36,6 +36,7 @@ EXPORTS = [
     "dfk_closer_build", "dfk_closer_build_arrays", "dfk_closer_stats", "dfk_closer_fetch", "dfk_closer_write",
     "dfk_partners_build", "dfk_partners_build_arrays", "dfk_partners_stats", "dfk_partners_fetch", "dfk_partners_write",
     "dfk_cons_build", "dfk_cons_build_arrays", "dfk_cons_stats", "dfk_cons_fetch", "dfk_cons_write",
+    "dfk_offsets_build", "dfk_offsets_build_arrays", "dfk_offsets_stats", "dfk_offsets_fetch", "dfk_offsets_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -65,6 +66,12 @@ CONS_WORDS = 24
 CONS = ["pairs", "stacks", "rows", "live", "rows_kept", "trimmed", "reversed", "columns", "cells", "decoded", "batches", "ranges", "us", "us_dims", "us_copy", "us_decode", "us_cons",
         "sum", "xor"]
 CONS_FILE = "a.close.cons"
+# dfk_offsets_stats' words (include/dfk.h, DFK_OFFSETS_*)
+OFFSETS_WORDS = 24
+OFFSETS = ["pairs", "candidates", "passed", "invalidated", "deleted_small", "survivors", "pairs_0", "pairs_1", "pairs_2", "pairs_more", "closable", "lookups", "batches",
+           "us", "us_candidates", "us_bits", "us_compact", "us_tail", "us_copy", "sum", "xor"]
+OFFSETS_FILE = "a.close.offsets"
+OFFSETS_RECORD = np.dtype([("offset", "<i4"), ("overlap", "<i4"), ("fraglen", "<i4"), ("mismatch", "<i4"), ("bits", "<f8"), ("state", "<u4"), ("zero", "<u4")])
 # dfk_adj_outcome's codes (include/dfk.h, DFK_ADJ_*)
 ADJ_OUTCOMES = ["not applicable", "used", "discarded: guess too low", "discarded: list problem", "no block", "dropped for an allocation",
                 "switched off"]
@@ -565,6 +572,41 @@ class Dfk:
     def cons_write(self, directory):
         """dfk_cons_write: a.close.cons into `directory` (which must exist)."""
         _check(lib().dfk_cons_write(self._ctx, None if directory is None else str(directory).encode()))
+
+    def offsets_build(self):
+        """dfk_offsets_build: GetOffsets1 per pair on the context's latest cons_build* result.  Returns offsets_stats()."""
+        _check(lib().dfk_offsets_build(self._ctx))
+        return self.offsets_stats()
+
+    def offsets_build_arrays(self, starts, bases, pairs_per_batch=0, directory=None):
+        """dfk_offsets_build_arrays: the same stage on arrays: starts uint64[2 p + 1], bases uint8[] (a byte a base, element 2 pi + ei the
+        consensus of side ei of pair pi); with a directory a.close.offsets is written there.  Returns offsets_stats()."""
+        n = 0 if starts is None else (len(starts) - 1) // 2
+        starts = None if starts is None else np.ascontiguousarray(starts, np.uint64)
+        # (an empty array still has an address: NULL is for what is left out on purpose)
+        bases = None if bases is None else np.ascontiguousarray(bases if len(bases) else np.zeros(1, np.uint8), np.uint8)
+        _check(lib().dfk_offsets_build_arrays(self._ctx, C.c_uint64(n), _p(starts), _p(bases), C.c_uint64(pairs_per_batch), None if directory is None else str(directory).encode()))
+        return self.offsets_stats()
+
+    def offsets_stats(self):
+        """dfk_offsets_stats: {counter: value} -- pairs, candidates, passed, invalidated, deleted as small, survivors, pairs with 0 / 1 / 2 /
+        more survivors, closable pairs, look-ups, batches, times, digest."""
+        out = (C.c_uint64 * OFFSETS_WORDS)()
+        _check(lib().dfk_offsets_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(OFFSETS)}
+
+    def offsets_fetch(self):
+        """dfk_offsets_fetch: dict(starts uint64[p + 1] in records, words uint32[p, 4] (candidates, passed, survivors, 0), records
+        OFFSETS_RECORD[passed])."""
+        npairs, nr = C.c_uint64(), C.c_uint64()
+        _check(lib().dfk_offsets_fetch(self._ctx, None, None, C.byref(npairs), None, C.c_uint64(0), C.byref(nr)))
+        starts, words, recs = np.zeros(npairs.value + 1, np.uint64), np.zeros((max(1, npairs.value), 4), np.uint32), np.zeros(max(1, nr.value), OFFSETS_RECORD)
+        _check(lib().dfk_offsets_fetch(self._ctx, _p(starts), _p(words), C.byref(npairs), _p(recs), C.c_uint64(nr.value), C.byref(nr)))
+        return dict(starts=starts, words=words[: npairs.value], records=recs[: nr.value])
+
+    def offsets_write(self, directory):
+        """dfk_offsets_write: a.close.offsets into `directory` (which must exist)."""
+        _check(lib().dfk_offsets_write(self._ctx, None if directory is None else str(directory).encode()))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
