@@ -646,6 +646,59 @@ int dfk_offsets_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_OFFSETS_WORDS] */);
 int dfk_offsets_fetch(dfk_ctx* ctx, uint64_t* starts, uint32_t* words, uint64_t* n_pairs, void* records, uint64_t records_cap, uint64_t* n_records);
 int dfk_offsets_write(dfk_ctx* ctx, const char* dir);
 
+/* ---- the eighth step of the patching stage: CloseGap2's closures per pair (10X/Closomatic.cc:651-660) ----
+ * The function's last statements, and the only thing it returns: for a pair with one or two surviving offsets the two stacks merged at
+ * each offset (ReadStack.cc:355-398) and Consensus1 with qualities of the merged stack (:406-427): the base of the greatest (sum, id)
+ * pair, so ties go to the HIGHEST base and a column nothing was added to gives base 3.  The sums run over stack 0's rows, then stack
+ * 1's, one IEEE double after the other.  No stack is stored.  Where both stacks have no rows (the reference reads an empty vector) the
+ * closure is C columns of base 3 and DFK_CLOSURES_ROWLESS counts it.  The rule, the plan and the file's layout: csrc/dfk_closures.h.
+ *   dfk_closures_build  works from the context's dfk_cons_build result (with the closer sets and partners it was made from still in
+ *                       place) and the dfk_offsets_build result made FROM THAT consensus: DFK_E_STATE without either, when the latest
+ *                       consensus or the offsets came from a *_build_arrays call, or when the offsets were made from an older
+ *                       consensus.  The read arguments are checked as dfk_cons_build checks them.
+ *   dfk_closures_build_arrays  the same stage on host arrays: dfk_cons_build_arrays' arguments, then off_first [n_pairs + 1] and the
+ *                       int32 offsets of every pair (the rule :651 is applied to the list given), closures_per_batch 0 = what fits;
+ *                       with a dir the file is written there.  DFK_E_ARG for an offset outside [-cols2, cols1] of its pair (so a
+ *                       merged stack is never wider than 800 columns; abutting stacks are allowed), starts that fall, null arguments.
+ *   A refused call changes nothing: dfk_closures_stats / _fetch / _write serve the latest result of either build until the next one.
+ *   dfk_closures_stats  out[DFK_CLOSURES_WORDS]: the counters below
+ *   dfk_closures_fetch  pair_first ([n_pairs + 1] words: the first closure of each pair, or NULL), starts ([n_closures + 1] words, in
+ *                       bases, or NULL), records (4 u32 a closure: pair, offset as i32, cols, rows, or NULL), the bases a byte each;
+ *                       NULL with cap 0 gives the counts alone; a buffer too small DFK_E_ARG, the counts still told.
+ *   dfk_closures_write  into dir (which must exist), whole or not at all.  Little-endian, no byte undefined:
+ *                         a.close.closures  "DFKCCLS1" | u64 n closures | u64 n_pairs | (n_pairs + 1) x u64 first closure of each pair |
+ *                                       (n + 1) x u64 starts, in bases | n x 16-byte { u32 pair, i32 offset, u32 cols, u32 rows }, rows
+ *                                       = rows_kept of both stacks | the bases, a byte each (0..3) | zero bytes to a multiple of 8. */
+#define DFK_CLOSURES_WORDS 24
+#define DFK_CLOSURES_PAIRS 0         /* pairs */
+#define DFK_CLOSURES_CLOSABLE 1      /* pairs with one or two offsets (:651): the only ones whose stacks are touched, */
+#define DFK_CLOSURES_OVER 2          /* pairs left out for more than two offsets */
+#define DFK_CLOSURES_CLOSURES 3      /* closures: one per offset of a closable pair */
+#define DFK_CLOSURES_COLUMNS 4       /* columns of all merged stacks: the bases of the result */
+#define DFK_CLOSURES_CELLS 5         /* defined cells added to a column's sums */
+#define DFK_CLOSURES_LIVE 6          /* live rows walked, summed over the closures */
+#define DFK_CLOSURES_EMPTY 7         /* columns nothing was added to (base 3) */
+#define DFK_CLOSURES_SHORT 8         /* closures shorter than K (MapClosures drops them later; here they are only counted) */
+#define DFK_CLOSURES_ROWLESS 9       /* closures of two stacks without rows */
+#define DFK_CLOSURES_BATCHES 10      /* batches of closures */
+#define DFK_CLOSURES_RANGES 11       /* ranges of pairs the dimensions and live rows were found in */
+#define DFK_CLOSURES_US 12           /* microseconds: the build call, */
+#define DFK_CLOSURES_US_DIMS 13      /* the uploads of the tables and lengths, dimensions and live rows, */
+#define DFK_CLOSURES_US_COPY 14      /* the gather of the reads on the host and the copies either way, */
+#define DFK_CLOSURES_US_DECODE 15    /* the decode, */
+#define DFK_CLOSURES_US_CONS 16      /* the merged consensus */
+#define DFK_CLOSURES_SUM 17          /* sum and xor over positions i of h(i, value) (k_digest_seq, salt 0xF1F1): the records as u32 words, then the bases one value each */
+#define DFK_CLOSURES_XOR 18
+int dfk_closures_build(dfk_ctx* ctx, const uint8_t* packed_bases, const uint64_t* base_off /* or NULL: dense */, const uint32_t* read_len, const uint8_t* pq, const uint64_t* pq_off,
+                       uint64_t n_reads);
+int dfk_closures_build_arrays(dfk_ctx* ctx, uint64_t n_edges, const int32_t* inv, const int32_t* kmers, uint64_t n_ce, const uint64_t* ce, const uint64_t* loc_first, const uint64_t* locs,
+                              const uint64_t* part_first, const uint64_t* parts, const int32_t* pairs, uint64_t n_pairs, const uint8_t* packed_bases, const uint64_t* base_off,
+                              const uint32_t* read_len, const uint8_t* pq, const uint64_t* pq_off, uint64_t n_reads, const uint64_t* off_first /* [n_pairs + 1] */, const int32_t* offsets,
+                              uint64_t closures_per_batch /* 0 = what fits */, const char* dir /* NULL = no file */);
+int dfk_closures_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_CLOSURES_WORDS] */);
+int dfk_closures_fetch(dfk_ctx* ctx, uint64_t* pair_first, uint64_t* starts, uint32_t* records, uint64_t* n_pairs, uint64_t* n_closures, uint8_t* bases, uint64_t bases_cap, uint64_t* n_bases);
+int dfk_closures_write(dfk_ctx* ctx, const char* dir);
+
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).
  * dfk_paths_digest  fills out[DFK_CHECK_WORDS] with digests that depend on the CONTENT of a.paths, a.paths.inv, a.countsb and

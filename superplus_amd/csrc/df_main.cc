@@ -552,7 +552,7 @@ int main(int argc, char** argv)
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
         {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
-        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -594,6 +594,11 @@ int main(int argc, char** argv)
     // OFFSETS=True (CloseGap2's stack offsets per pair, GetOffsets1, a.<K>/a.close.offsets) works from the two consensus sequences of a pair
     if (truthy(a["OFFSETS"]) && !want_cons) give_up("OFFSETS=True needs CONS=True: the offsets are found between the two stack consensus sequences of a pair");
     const bool want_offsets = truthy(a["OFFSETS"]);
+
+    // CLOSURES=True (CloseGap2's closures per pair, Closomatic.cc:651-660, a.<K>/a.close.closures) merges the two stacks of a pair at its surviving
+    // offsets: it reads the reads and their qualities once more (the maps stay, as for CONS=True), and like HOPS=True it runs on one GPU only
+    if (truthy(a["CLOSURES"]) && !want_offsets) give_up("CLOSURES=True needs OFFSETS=True: a pair's stacks are merged at the offsets GetOffsets1 returned");
+    const bool want_closures = truthy(a["CLOSURES"]);
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -1087,6 +1092,18 @@ int main(int argc, char** argv)
                                    (unsigned long long)os[DFK_OFFSETS_DELETED_SMALL], (unsigned long long)os[DFK_OFFSETS_SURVIVORS], (unsigned long long)os[DFK_OFFSETS_SUM], (unsigned long long)os[DFK_OFFSETS_XOR],
                                    (unsigned long long)os[DFK_OFFSETS_PAIRS_0], (unsigned long long)os[DFK_OFFSETS_PAIRS_1], (unsigned long long)os[DFK_OFFSETS_PAIRS_2], (unsigned long long)os[DFK_OFFSETS_PAIRS_MORE],
                                    (unsigned long long)os[DFK_OFFSETS_CLOSABLE], (unsigned long long)os[DFK_OFFSETS_LOOKUPS], (unsigned long long)os[DFK_OFFSETS_BATCHES]);
+                        }
+                        if (want_closures) {                                    // the closures themselves (Closomatic.cc:651-660): a.<K>/a.close.closures, after a.close.offsets
+                            uint64_t cs[DFK_CLOSURES_WORDS] = {};
+                            const int crc = fast ? dfk_closures_build(ctx, h_packed + (n_reads ? ld64(h_boff) : 0), nullptr, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, n_reads)      // (dense: validated at load)
+                                                 : dfk_closures_build(ctx, h_packed, (const uint64_t*)h_boff, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, n_reads);
+                            if (crc || dfk_closures_write(ctx, dir.c_str()) || dfk_closures_stats(ctx, cs)) throw std::runtime_error(dfk_last_error());
+                            printf("DF_CLOSURES {\"pairs\": %llu, \"closable\": %llu, \"over\": %llu, \"closures\": %llu, \"columns\": %llu, \"a.close.closures\": \"%016llx%016llx\", \"cells\": %llu, "
+                                   "\"live_rows\": %llu, \"empty\": %llu, \"short\": %llu, \"rowless\": %llu, \"batches\": %llu, \"ranges\": %llu}\n",
+                                   (unsigned long long)cs[DFK_CLOSURES_PAIRS], (unsigned long long)cs[DFK_CLOSURES_CLOSABLE], (unsigned long long)cs[DFK_CLOSURES_OVER], (unsigned long long)cs[DFK_CLOSURES_CLOSURES],
+                                   (unsigned long long)cs[DFK_CLOSURES_COLUMNS], (unsigned long long)cs[DFK_CLOSURES_SUM], (unsigned long long)cs[DFK_CLOSURES_XOR], (unsigned long long)cs[DFK_CLOSURES_CELLS],
+                                   (unsigned long long)cs[DFK_CLOSURES_LIVE], (unsigned long long)cs[DFK_CLOSURES_EMPTY], (unsigned long long)cs[DFK_CLOSURES_SHORT], (unsigned long long)cs[DFK_CLOSURES_ROWLESS],
+                                   (unsigned long long)cs[DFK_CLOSURES_BATCHES], (unsigned long long)cs[DFK_CLOSURES_RANGES]);
                         }
                     }
                 }

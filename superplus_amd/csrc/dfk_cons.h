@@ -209,7 +209,9 @@ inline int32_t bases_of_edge(const Input& I, uint64_t e) { return (int32_t)((int
 // ---- the literal transcription for one pair and side: Closomatic.cc:589-640 and the readstack's members as they stand, the stack
 // materialised.  -3: a read's PQVec stream does not hold len values
 struct Triple { int64_t id; int pos; bool fw; };
-inline int stack_literal(const Input& I, int32_t e2, uint64_t e, const std::vector<Triple>& locs, Dim* dim, std::vector<uint8_t>* con, HostResult* counters)
+// the stack as it stands after Trim and Reverse (:598-638): what Consensus1 below and Merge (dfk_closures.h) take
+struct Grids { std::vector<std::vector<int8_t>> bases_, quals_; int rows = 0, cols = 0; };
+inline int stack_grids(const Input& I, int32_t e2, uint64_t e, const std::vector<Triple>& locs, Dim* dim, Grids* G, HostResult* counters)
 {
     const int ne = bases_of_edge(I, e);                                                          // :592
     auto len_of = [&](int64_t id) { return (int)I.read_len[id]; };
@@ -261,6 +263,15 @@ inline int stack_literal(const Input& I, int32_t e2, uint64_t e, const std::vect
         ++counters->reversed;
     }
     dim->rows_kept = (uint32_t)rows; dim->cols = (uint32_t)cols;
+    G->bases_.swap(bases_); G->quals_.swap(quals_); G->rows = rows; G->cols = cols;
+    return 0;
+}
+inline int stack_literal(const Input& I, int32_t e2, uint64_t e, const std::vector<Triple>& locs, Dim* dim, std::vector<uint8_t>* con, HostResult* counters)
+{
+    Grids G;
+    if (int rc = stack_grids(I, e2, e, locs, dim, &G, counters)) return rc;
+    const std::vector<std::vector<int8_t>>& bases_ = G.bases_; const std::vector<std::vector<int8_t>>& quals_ = G.quals_;
+    const int rows = G.rows, cols = G.cols;
     con->assign((size_t)cols, 0);
     for (int c = 0; c < cols; c++) {                                                             // ReadStack.cc:400-404
         double sum[4]{0., 0., 0., 0.};                                                           // :1846

@@ -49,6 +49,8 @@ struct HostGraph {
     void (*cons_free)(struct ConsResult*) = nullptr;
     struct OffsetsResult* offsets = nullptr;                         // the latest dfk_offsets_build*'s result (dfk_offsets.inc)
     void (*offsets_free)(struct OffsetsResult*) = nullptr;
+    struct ClosuresResult* closures = nullptr;                       // the latest dfk_closures_build*'s result (dfk_closures.inc)
+    void (*closures_free)(struct ClosuresResult*) = nullptr;
     ~HostGraph()
     {
         if (paths && paths_free) paths_free(paths);
@@ -58,6 +60,7 @@ struct HostGraph {
         if (partners_arrays && partners_free) partners_free(partners_arrays);
         if (cons_arrays && cons_free) cons_free(cons_arrays);
         if (offsets && offsets_free) offsets_free(offsets);
+        if (closures && closures_free) closures_free(closures);
     }
 };
 

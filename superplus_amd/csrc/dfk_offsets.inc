@@ -14,6 +14,7 @@ struct OffsetsResult {
     std::vector<dfk_offsets::PairWords> words;    // [n_pairs]
     std::vector<dfk_offsets::Rec> recs;
     uint64_t stats[DFK_OFFSETS_WORDS] = {};
+    uint64_t cons_serial = 0;                     // dfk_offsets_build: the consensus it was made from (0: from arrays); dfk_closures_build asks
 };
 void offsets_result_free(OffsetsResult* r) { delete r; }
 
@@ -208,6 +209,7 @@ int dfk_offsets_build(dfk_ctx* c)
     HIP_TRY(hipSetDevice(c->device));
     std::unique_ptr<OffsetsResult> R(new OffsetsResult);
     if (int rc = offsets_build(c, n / 2, C->starts.data(), C->bases.data(), 0, R.get())) return rc;     // (refused: the earlier result is still served)
+    R->cons_serial = C->serial;
     offsets_keep(c, R.release());
     return 0;
     });

@@ -37,6 +37,7 @@ EXPORTS = [
     "dfk_partners_build", "dfk_partners_build_arrays", "dfk_partners_stats", "dfk_partners_fetch", "dfk_partners_write",
     "dfk_cons_build", "dfk_cons_build_arrays", "dfk_cons_stats", "dfk_cons_fetch", "dfk_cons_write",
     "dfk_offsets_build", "dfk_offsets_build_arrays", "dfk_offsets_stats", "dfk_offsets_fetch", "dfk_offsets_write",
+    "dfk_closures_build", "dfk_closures_build_arrays", "dfk_closures_stats", "dfk_closures_fetch", "dfk_closures_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -72,6 +73,11 @@ OFFSETS = ["pairs", "candidates", "passed", "invalidated", "deleted_small", "sur
            "us", "us_candidates", "us_bits", "us_compact", "us_tail", "us_copy", "sum", "xor"]
 OFFSETS_FILE = "a.close.offsets"
 OFFSETS_RECORD = np.dtype([("offset", "<i4"), ("overlap", "<i4"), ("fraglen", "<i4"), ("mismatch", "<i4"), ("bits", "<f8"), ("state", "<u4"), ("zero", "<u4")])
+# dfk_closures_stats' words (include/dfk.h, DFK_CLOSURES_*)
+CLOSURES_WORDS = 24
+CLOSURES = ["pairs", "closable", "over", "closures", "columns", "cells", "live", "empty", "short", "rowless", "batches", "ranges", "us", "us_dims", "us_copy", "us_decode", "us_cons",
+            "sum", "xor"]
+CLOSURES_FILE = "a.close.closures"
 # dfk_adj_outcome's codes (include/dfk.h, DFK_ADJ_*)
 ADJ_OUTCOMES = ["not applicable", "used", "discarded: guess too low", "discarded: list problem", "no block", "dropped for an allocation",
                 "switched off"]
@@ -607,6 +613,56 @@ class Dfk:
     def offsets_write(self, directory):
         """dfk_offsets_write: a.close.offsets into `directory` (which must exist)."""
         _check(lib().dfk_offsets_write(self._ctx, None if directory is None else str(directory).encode()))
+
+    def closures_build(self, packed, base_off, read_len, pq_bytes, pq_off):
+        """dfk_closures_build: CloseGap2's closures per pair, after cons_build and the offsets_build made from that consensus.  The reads
+        are the pathed ones, as cons_build takes them.  Returns closures_stats()."""
+        n = 0 if read_len is None else len(read_len)
+        packed, read_len, pq_bytes = (None if x is None else np.ascontiguousarray(x, t) for x, t in ((packed, np.uint8), (read_len, np.uint32), (pq_bytes, np.uint8)))
+        base_off, pq_off = (None if x is None else np.ascontiguousarray(x, np.uint64) for x in (base_off, pq_off))
+        _check(lib().dfk_closures_build(self._ctx, _p(packed), _p(base_off), _p(read_len), _p(pq_bytes), _p(pq_off), C.c_uint64(n)))
+        return self.closures_stats()
+
+    def closures_build_arrays(self, a, off_first, offsets, closures_per_batch=0, directory=None, **change):
+        """dfk_closures_build_arrays: the same stage on arrays.  a: what cons_build_arrays takes; off_first uint64[p + 1] and offsets int32[]
+        the offsets of every pair (a pair with none or more than two gets no closure); with a directory a.close.closures is written there.
+        Returns closures_stats()."""
+        a = dict(a); a.update(change)
+        kinds = dict(inv=np.int32, kmers=np.int32, ce=np.uint64, loc_first=np.uint64, locs=np.uint64, part_first=np.uint64, parts=np.uint64, pairs=np.int32,
+                     read_packed=np.uint8, read_off=np.uint64, read_len=np.uint32, pq=np.uint8, pq_off=np.uint64)
+        n = {k: (0 if a[k] is None else len(a[k])) for k in kinds}
+        # (an empty array still has an address: NULL is for what is left out on purpose)
+        v = {k: None if a[k] is None else np.ascontiguousarray(a[k] if len(a[k]) else np.zeros(1, t), t) for k, t in kinds.items()}
+        off_first = None if off_first is None else np.ascontiguousarray(off_first, np.uint64)
+        offsets = None if offsets is None else np.ascontiguousarray(offsets if len(offsets) else np.zeros(1, np.int32), np.int32)
+        _check(lib().dfk_closures_build_arrays(self._ctx, C.c_uint64(n["inv"]), _p(v["inv"]), _p(v["kmers"]), C.c_uint64(n["ce"]), _p(v["ce"]), _p(v["loc_first"]), _p(v["locs"]),
+                                               _p(v["part_first"]), _p(v["parts"]), _p(v["pairs"]), C.c_uint64(n["pairs"]), _p(v["read_packed"]), _p(v["read_off"]), _p(v["read_len"]),
+                                               _p(v["pq"]), _p(v["pq_off"]), C.c_uint64(n["read_len"]), _p(off_first), _p(offsets), C.c_uint64(closures_per_batch),
+                                               None if directory is None else str(directory).encode()))
+        return self.closures_stats()
+
+    def closures_stats(self):
+        """dfk_closures_stats: {counter: value} -- pairs, closable pairs, pairs left out for more than two offsets, closures, columns, cells
+        added, live rows walked, empty columns, closures shorter than K, rowless closures, batches, ranges, times, digest."""
+        out = (C.c_uint64 * CLOSURES_WORDS)()
+        _check(lib().dfk_closures_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(CLOSURES)}
+
+    def closures_fetch(self):
+        """dfk_closures_fetch: dict(pair_first uint64[p + 1], starts uint64[n + 1], records int64[n, 4] (pair, offset, cols, rows), bases
+        uint8[columns])."""
+        npairs, nc, nb = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().dfk_closures_fetch(self._ctx, None, None, None, C.byref(npairs), C.byref(nc), None, C.c_uint64(0), C.byref(nb)))
+        pair_first, starts = np.zeros(npairs.value + 1, np.uint64), np.zeros(nc.value + 1, np.uint64)
+        recs, bases = np.zeros((max(1, nc.value), 4), np.uint32), np.zeros(max(1, nb.value), np.uint8)
+        _check(lib().dfk_closures_fetch(self._ctx, _p(pair_first), _p(starts), _p(recs), C.byref(npairs), C.byref(nc), _p(bases), C.c_uint64(nb.value), C.byref(nb)))
+        recs = recs[: nc.value].astype(np.int64)
+        recs[:, 1] = recs[:, 1].astype(np.uint32).view(np.int32) if len(recs) else recs[:, 1]
+        return dict(pair_first=pair_first, starts=starts, records=recs, bases=bases[: nb.value])
+
+    def closures_write(self, directory):
+        """dfk_closures_write: a.close.closures into `directory` (which must exist)."""
+        _check(lib().dfk_closures_write(self._ctx, None if directory is None else str(directory).encode()))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
