@@ -699,6 +699,77 @@ int dfk_closures_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_CLOSURES_WORDS] */);
 int dfk_closures_fetch(dfk_ctx* ctx, uint64_t* pair_first, uint64_t* starts, uint32_t* records, uint64_t* n_pairs, uint64_t* n_closures, uint8_t* bases, uint64_t bases_cap, uint64_t* n_bases);
 int dfk_closures_write(dfk_ctx* ctx, const char* dir);
 
+/* ---- the second closer's walks: Stackster's two stack walks per pair (10X/Stackster.cc:207-262 StackWalk, :326-414) ----
+ * Stackster loads the reads of a pair's set (a.close.reads of es = { e1, inv[e2] } composed), lowers their qualities in homopolymers of 20
+ * bases or more, orients them, and for side 0 then side 1 extends the edge's first 48-mer base by base through the set's reads
+ * (k = 48 whatever the graph's K): a read is placed by the first step whose 48-mer it holds once, at start = |EE| - 48 - pos; a base is
+ * appended while the largest quality sum under it is >= 60 and >= twice the second.  Kept per pair and side: |E|, |EE|, the bases of
+ * EE, the steps that met a duplicate, M = max( start + len ), trim = max( 0, M - 400 ), and per placed entry ( id, start, fw ^ side ):
+ * the locs the stacks are built from.  No stack is stored.  Side 1 is not walked where side 0 placed nobody (Stackster returns); an
+ * edge of fewer than 48 bases (K < 48 only) is not walked.  The rule, the plan and the file's layout: csrc/dfk_walks.h.
+ *   dfk_walks_build   works from the context's dfk_closer_build result and the graph's edges; pairs NULL: the dfk_hops_build pairs.  The
+ *                     read arguments are the pathed reads with their PQVec qualities, checked as dfk_cons_build checks them.
+ *   dfk_walks_build_arrays  the same stage on host arrays: inv and kmers per edge, the bases of EVERY edge 2-bit packed with their byte
+ *                     offsets [n_edges + 1] (a.fastb's data), ce ascending, read_first [n_ce + 1] and the sets as dfk_closer_fetch gives
+ *                     them ( id << 1 | fw, ascending and distinct per rank ), the pairs, the reads; walks_per_batch 0 = what fits (a batch
+ *                     holds whole pairs: ( w + 1 ) / 2 of them); with a dir the file is written there.
+ *   DFK_E_ARG for a pair's edge outside the graph or not among ce, tables that fall, null arguments, and for a set of 2^23 entries or
+ *   more (the reference's int sums could overflow there); DFK_E_INPUT for a PQVec stream that does not hold its read's length.  A
+ *   refused call changes nothing: dfk_walks_stats / _fetch / _write serve the latest result of either build, hbm_held is as before.
+ *   A walk whose live list (placed entries that still cover the current column) outgrows DFK_WALK_MAX_LIVE (1024) is done exactly on
+ *   the host and counted (DFK_WALKS_HOST_ROUTE); the environment's DFK_WALK_MAX_LIVE (smaller) and DFK_WALK_HASH_BITS (fewer than 64)
+ *   are for tests: they force that route, and collisions of the table's hash, which cost time and never change a byte.
+ *   dfk_walks_stats   out[DFK_WALKS_WORDS]: the counters below
+ *   dfk_walks_fetch   starts and ee_starts ([n_walks + 1] words each, or NULL), records (8 u32 a walk, or NULL), the placed records (16
+ *                     bytes each) and the EE bases a byte each; NULL with cap 0 gives the counts alone; a buffer too small DFK_E_ARG.
+ *   dfk_walks_write   into dir (which must exist), whole or not at all.  Little-endian, no byte undefined:
+ *                       a.stack.walks  "DFKSWLK1" | u64 n = 2 * n_pairs | (n + 1) x u64 first placed record of each walk | (n + 1) x u64
+ *                                     first base of each EE | n x 32-byte { u32 status (0 walked, 1 not walked: side 0 placed nobody, 2 the
+ *                                     edge is shorter than 48), u32 entries, u32 placed, u32 dup_steps, i32 nE, u32 nEE, i32 M, i32 trim } |
+ *                                     the placed records { i64 id, i32 start, u32 fw } | the EE bases four a byte, the first in the low
+ *                                     bits | zero bytes to a multiple of 8.  Element 2 pi + s is side s of pair pi. */
+#define DFK_WALKS_WORDS 32
+#define DFK_WALKS_PAIRS 0            /* pairs */
+#define DFK_WALKS_WALKS 1            /* sides walked */
+#define DFK_WALKS_ENTRIES 2          /* set entries of the walked sides */
+#define DFK_WALKS_PLACED 3           /* entries placed: the placed records */
+#define DFK_WALKS_EE 4               /* bases of all EE */
+#define DFK_WALKS_LONGEST 5          /* the longest EE */
+#define DFK_WALKS_DUP_STEPS 6        /* steps that placed nobody because an entry held the 48-mer twice */
+#define DFK_WALKS_STEPS 7            /* steps */
+#define DFK_WALKS_PAST_EDGE 8        /* walks whose EE is longer than their edge */
+#define DFK_WALKS_SIDE0_EMPTY 9      /* pairs whose side 0 placed nobody (side 1 not walked) */
+#define DFK_WALKS_SIDE1_EMPTY 10     /* pairs whose side 1 was walked and placed nobody */
+#define DFK_WALKS_SHORT 11           /* sides not walked for an edge shorter than 48 bases */
+#define DFK_WALKS_TRIMMED 12         /* sides with M > 400 */
+#define DFK_WALKS_YIELDS 13          /* pairs with entries placed on both sides */
+#define DFK_WALKS_LIVE_SUM 14        /* live entries summed over the steps */
+#define DFK_WALKS_LIVE_MAX 15        /* the longest live list */
+#define DFK_WALKS_HOST_ROUTE 16      /* walks done on the host: their live list outgrew its room */
+#define DFK_WALKS_VERIFIED 17        /* table hits whose 48 bases matched, */
+#define DFK_WALKS_COLLISIONS 18      /* and hits of the hash alone (device walks) */
+#define DFK_WALKS_KMERS 19           /* 48-mers sorted, both sides */
+#define DFK_WALKS_DECODED 20         /* reads gathered, decoded and lowered, a read once a batch */
+#define DFK_WALKS_BATCHES 21         /* batches of pairs */
+#define DFK_WALKS_RANGES 22          /* ranges of pairs */
+#define DFK_WALKS_US 23              /* microseconds: the build call, */
+#define DFK_WALKS_US_COPY 24         /* the gather of the reads on the host and their copies, */
+#define DFK_WALKS_US_DECODE 25       /* decode and lowering, */
+#define DFK_WALKS_US_SORT 26         /* the tables: 48-mers, hashes, sorts, */
+#define DFK_WALKS_US_WALK 27         /* the walk kernel with its copies back */
+#define DFK_WALKS_SUM 28             /* sum and xor over positions i of h(i, value) (k_digest_seq, salt 0xABAB): the records as u32 words, the placed records as u64 words, the EE bases */
+#define DFK_WALKS_XOR 29
+int dfk_walks_build(dfk_ctx* ctx, const int32_t* pairs /* or NULL */, uint64_t n_pairs, const uint8_t* packed_bases, const uint64_t* base_off /* or NULL: dense */, const uint32_t* read_len,
+                    const uint8_t* pq, const uint64_t* pq_off, uint64_t n_reads);
+int dfk_walks_build_arrays(dfk_ctx* ctx, uint64_t n_edges, const int32_t* inv, const int32_t* kmers, const uint8_t* edge_packed, const uint64_t* edge_off /* [n_edges + 1], bytes */, uint64_t n_ce,
+                           const uint64_t* ce, const uint64_t* read_first /* [n_ce + 1] */, const uint64_t* reads, const int32_t* pairs, uint64_t n_pairs, const uint8_t* packed_bases,
+                           const uint64_t* base_off, const uint32_t* read_len, const uint8_t* pq, const uint64_t* pq_off, uint64_t n_reads, uint64_t walks_per_batch /* 0 = what fits */,
+                           const char* dir /* NULL = no file */);
+int dfk_walks_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_WALKS_WORDS] */);
+int dfk_walks_fetch(dfk_ctx* ctx, uint64_t* starts, uint64_t* ee_starts, uint32_t* records, uint64_t* n_walks, void* placed, uint64_t placed_cap, uint64_t* n_placed, uint8_t* bases, uint64_t bases_cap,
+                    uint64_t* n_bases);
+int dfk_walks_write(dfk_ctx* ctx, const char* dir);
+
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).
  * dfk_paths_digest  fills out[DFK_CHECK_WORDS] with digests that depend on the CONTENT of a.paths, a.paths.inv, a.countsb and

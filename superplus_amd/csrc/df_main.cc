@@ -552,7 +552,7 @@ int main(int argc, char** argv)
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
         {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
-        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}, {"WALKS", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -599,6 +599,11 @@ int main(int argc, char** argv)
     // offsets: it reads the reads and their qualities once more (the maps stay, as for CONS=True), and like HOPS=True it runs on one GPU only
     if (truthy(a["CLOSURES"]) && !want_offsets) give_up("CLOSURES=True needs OFFSETS=True: a pair's stacks are merged at the offsets GetOffsets1 returned");
     const bool want_closures = truthy(a["CLOSURES"]);
+
+    // WALKS=True (Stackster's two stack walks per pair, Stackster.cc:207-262 and :326-414, a.<K>/a.stack.walks) works from the closers' read sets, the
+    // edges' bases and the reads with their qualities (the maps stay, as for CONS=True); like HOPS=True, which CLOSER=True needs, it runs on one GPU only
+    if (truthy(a["WALKS"]) && !truthy(a["CLOSER"])) give_up("WALKS=True needs CLOSER=True: a walk runs through the read set the closers made for its pair");
+    const bool want_walks = truthy(a["WALKS"]);
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -952,7 +957,7 @@ int main(int argc, char** argv)
             // of one thread's page-table work -- at exit, if not before.  Behind the tasks that still read the maps.
             auto earlier = std::make_shared<std::vector<std::thread>>(std::move(background));
             background.clear();
-            background.emplace_back([&ins, earlier, want_partners, want_cons] { for (auto& x : *earlier) x.join(); for (In& x : ins) { if (!want_partners) x.fb.m.unmap(); if (!want_cons) x.qp.m.unmap(); } });      // (PARTNERS=True reads the bases of some reads again, CONS=True their qualities too)
+            background.emplace_back([&ins, earlier, want_partners, want_cons, want_walks] { for (auto& x : *earlier) x.join(); for (In& x : ins) { if (!want_partners && !want_walks) x.fb.m.unmap(); if (!want_cons && !want_walks) x.qp.m.unmap(); } });      // (PARTNERS=True reads the bases of some reads again, CONS=True their qualities too, WALKS=True both)
         }
         mark("count joined");
         t0 = now_s();
@@ -1104,6 +1109,20 @@ int main(int argc, char** argv)
                                    (unsigned long long)cs[DFK_CLOSURES_COLUMNS], (unsigned long long)cs[DFK_CLOSURES_SUM], (unsigned long long)cs[DFK_CLOSURES_XOR], (unsigned long long)cs[DFK_CLOSURES_CELLS],
                                    (unsigned long long)cs[DFK_CLOSURES_LIVE], (unsigned long long)cs[DFK_CLOSURES_EMPTY], (unsigned long long)cs[DFK_CLOSURES_SHORT], (unsigned long long)cs[DFK_CLOSURES_ROWLESS],
                                    (unsigned long long)cs[DFK_CLOSURES_BATCHES], (unsigned long long)cs[DFK_CLOSURES_RANGES]);
+                        }
+                        if (want_walks) {                                       // Stackster's two stack walks per pair (Stackster.cc:207-262, :326-414): a.<K>/a.stack.walks, after a.close.*
+                            uint64_t ws[DFK_WALKS_WORDS] = {};
+                            const int wrc = fast ? dfk_walks_build(ctx, nullptr, 0, h_packed + (n_reads ? ld64(h_boff) : 0), nullptr, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, n_reads)      // (dense: validated at load)
+                                                 : dfk_walks_build(ctx, nullptr, 0, h_packed, (const uint64_t*)h_boff, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, n_reads);
+                            if (wrc || dfk_walks_write(ctx, dir.c_str()) || dfk_walks_stats(ctx, ws)) throw std::runtime_error(dfk_last_error());
+                            printf("DF_WALKS {\"pairs\": %llu, \"walks\": %llu, \"entries\": %llu, \"placed\": %llu, \"bases\": %llu, \"longest\": %llu, \"a.stack.walks\": \"%016llx%016llx\", \"steps\": %llu, "
+                                   "\"dup_steps\": %llu, \"past_edge\": %llu, \"side0_empty\": %llu, \"side1_empty\": %llu, \"short\": %llu, \"trimmed\": %llu, \"yields\": %llu, \"live_max\": %llu, "
+                                   "\"host_route\": %llu, \"batches\": %llu, \"ranges\": %llu}\n",
+                                   (unsigned long long)ws[DFK_WALKS_PAIRS], (unsigned long long)ws[DFK_WALKS_WALKS], (unsigned long long)ws[DFK_WALKS_ENTRIES], (unsigned long long)ws[DFK_WALKS_PLACED],
+                                   (unsigned long long)ws[DFK_WALKS_EE], (unsigned long long)ws[DFK_WALKS_LONGEST], (unsigned long long)ws[DFK_WALKS_SUM], (unsigned long long)ws[DFK_WALKS_XOR],
+                                   (unsigned long long)ws[DFK_WALKS_STEPS], (unsigned long long)ws[DFK_WALKS_DUP_STEPS], (unsigned long long)ws[DFK_WALKS_PAST_EDGE], (unsigned long long)ws[DFK_WALKS_SIDE0_EMPTY],
+                                   (unsigned long long)ws[DFK_WALKS_SIDE1_EMPTY], (unsigned long long)ws[DFK_WALKS_SHORT], (unsigned long long)ws[DFK_WALKS_TRIMMED], (unsigned long long)ws[DFK_WALKS_YIELDS],
+                                   (unsigned long long)ws[DFK_WALKS_LIVE_MAX], (unsigned long long)ws[DFK_WALKS_HOST_ROUTE], (unsigned long long)ws[DFK_WALKS_BATCHES], (unsigned long long)ws[DFK_WALKS_RANGES]);
                         }
                     }
                 }

@@ -51,6 +51,8 @@ struct HostGraph {
     void (*offsets_free)(struct OffsetsResult*) = nullptr;
     struct ClosuresResult* closures = nullptr;                       // the latest dfk_closures_build*'s result (dfk_closures.inc)
     void (*closures_free)(struct ClosuresResult*) = nullptr;
+    struct WalksResult* walks = nullptr;                             // the latest dfk_walks_build*'s result (dfk_walks.inc)
+    void (*walks_free)(struct WalksResult*) = nullptr;
     ~HostGraph()
     {
         if (paths && paths_free) paths_free(paths);
@@ -61,6 +63,7 @@ struct HostGraph {
         if (cons_arrays && cons_free) cons_free(cons_arrays);
         if (offsets && offsets_free) offsets_free(offsets);
         if (closures && closures_free) closures_free(closures);
+        if (walks && walks_free) walks_free(walks);
     }
 };
 

@@ -38,6 +38,7 @@ EXPORTS = [
     "dfk_cons_build", "dfk_cons_build_arrays", "dfk_cons_stats", "dfk_cons_fetch", "dfk_cons_write",
     "dfk_offsets_build", "dfk_offsets_build_arrays", "dfk_offsets_stats", "dfk_offsets_fetch", "dfk_offsets_write",
     "dfk_closures_build", "dfk_closures_build_arrays", "dfk_closures_stats", "dfk_closures_fetch", "dfk_closures_write",
+    "dfk_walks_build", "dfk_walks_build_arrays", "dfk_walks_stats", "dfk_walks_fetch", "dfk_walks_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -78,6 +79,12 @@ CLOSURES_WORDS = 24
 CLOSURES = ["pairs", "closable", "over", "closures", "columns", "cells", "live", "empty", "short", "rowless", "batches", "ranges", "us", "us_dims", "us_copy", "us_decode", "us_cons",
             "sum", "xor"]
 CLOSURES_FILE = "a.close.closures"
+# dfk_walks_stats' words (include/dfk.h, DFK_WALKS_*)
+WALKS_WORDS = 32
+WALKS = ["pairs", "walks", "entries", "placed", "ee", "longest", "dup_steps", "steps", "past_edge", "side0_empty", "side1_empty", "short", "trimmed", "yields", "live_sum", "live_max",
+         "host_route", "verified", "collisions", "kmers", "decoded", "batches", "ranges", "us", "us_copy", "us_decode", "us_sort", "us_walk", "sum", "xor"]
+WALKS_FILE = "a.stack.walks"
+WALKS_PLACED = np.dtype([("id", "<i8"), ("start", "<i4"), ("fw", "<u4")])
 # dfk_adj_outcome's codes (include/dfk.h, DFK_ADJ_*)
 ADJ_OUTCOMES = ["not applicable", "used", "discarded: guess too low", "discarded: list problem", "no block", "dropped for an allocation",
                 "switched off"]
@@ -663,6 +670,53 @@ class Dfk:
     def closures_write(self, directory):
         """dfk_closures_write: a.close.closures into `directory` (which must exist)."""
         _check(lib().dfk_closures_write(self._ctx, None if directory is None else str(directory).encode()))
+
+    def walks_build(self, pairs, packed, base_off, read_len, pq_bytes, pq_off):
+        """dfk_walks_build: Stackster's two stack walks per pair, after closer_build.  pairs int32[p, 2] or None (the hops_build pairs); the
+        reads are the pathed ones with their PQVec qualities, as cons_build takes them.  Returns walks_stats()."""
+        n = 0 if read_len is None else len(read_len)
+        pairs = None if pairs is None else np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        packed, read_len, pq_bytes = (None if x is None else np.ascontiguousarray(x, t) for x, t in ((packed, np.uint8), (read_len, np.uint32), (pq_bytes, np.uint8)))
+        base_off, pq_off = (None if x is None else np.ascontiguousarray(x, np.uint64) for x in (base_off, pq_off))
+        _check(lib().dfk_walks_build(self._ctx, _p(pairs), C.c_uint64(0 if pairs is None else len(pairs)), _p(packed), _p(base_off), _p(read_len), _p(pq_bytes), _p(pq_off), C.c_uint64(n)))
+        return self.walks_stats()
+
+    def walks_build_arrays(self, a, walks_per_batch=0, directory=None, **change):
+        """dfk_walks_build_arrays: the same stage on arrays.  a: dict(inv, kmers int32[E], edge_packed uint8[], edge_off uint64[E + 1], ce
+        uint64[], read_first uint64[n_ce + 1], reads uint64[] (id << 1 | fw), pairs int32[p, 2], read_packed, read_off, read_len, pq,
+        pq_off); a key in `change` replaces one (None: a NULL pointer).  With a directory a.stack.walks is written there.  Returns
+        walks_stats()."""
+        a = dict(a); a.update(change)
+        kinds = dict(inv=np.int32, kmers=np.int32, edge_packed=np.uint8, edge_off=np.uint64, ce=np.uint64, read_first=np.uint64, reads=np.uint64, pairs=np.int32,
+                     read_packed=np.uint8, read_off=np.uint64, read_len=np.uint32, pq=np.uint8, pq_off=np.uint64)
+        n = {k: (0 if a[k] is None else len(a[k])) for k in kinds}
+        # (an empty array still has an address: NULL is for what is left out on purpose)
+        v = {k: None if a[k] is None else np.ascontiguousarray(a[k] if len(a[k]) else np.zeros(1, t), t) for k, t in kinds.items()}
+        _check(lib().dfk_walks_build_arrays(self._ctx, C.c_uint64(n["inv"]), _p(v["inv"]), _p(v["kmers"]), _p(v["edge_packed"]), _p(v["edge_off"]), C.c_uint64(n["ce"]), _p(v["ce"]),
+                                            _p(v["read_first"]), _p(v["reads"]), _p(v["pairs"]), C.c_uint64(n["pairs"]), _p(v["read_packed"]), _p(v["read_off"]), _p(v["read_len"]),
+                                            _p(v["pq"]), _p(v["pq_off"]), C.c_uint64(n["read_len"]), C.c_uint64(walks_per_batch), None if directory is None else str(directory).encode()))
+        return self.walks_stats()
+
+    def walks_stats(self):
+        """dfk_walks_stats: {counter: value} -- pairs, walks, entries, placed, bases walked, the longest walk, duplicate steps, steps, walks past
+        their edge, empty sides, short edges, trimmed sides, live entries, walks done on the host, table hits, batches, ranges, times, digest."""
+        out = (C.c_uint64 * WALKS_WORDS)()
+        _check(lib().dfk_walks_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(WALKS)}
+
+    def walks_fetch(self):
+        """dfk_walks_fetch: dict(starts uint64[n + 1], ee_starts uint64[n + 1], records uint32[n, 8] (status, entries, placed, dup_steps, nE,
+        nEE, M, trim), placed WALKS_PLACED[], bases uint8[])."""
+        n, nl, nb = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().dfk_walks_fetch(self._ctx, None, None, None, C.byref(n), None, C.c_uint64(0), C.byref(nl), None, C.c_uint64(0), C.byref(nb)))
+        starts, ee_starts = np.zeros(n.value + 1, np.uint64), np.zeros(n.value + 1, np.uint64)
+        recs, placed, bases = np.zeros((max(1, n.value), 8), np.uint32), np.zeros(max(1, nl.value), WALKS_PLACED), np.zeros(max(1, nb.value), np.uint8)
+        _check(lib().dfk_walks_fetch(self._ctx, _p(starts), _p(ee_starts), _p(recs), C.byref(n), _p(placed), C.c_uint64(nl.value), C.byref(nl), _p(bases), C.c_uint64(nb.value), C.byref(nb)))
+        return dict(starts=starts, ee_starts=ee_starts, records=recs[: n.value], placed=placed[: nl.value], bases=bases[: nb.value])
+
+    def walks_write(self, directory):
+        """dfk_walks_write: a.stack.walks into `directory` (which must exist)."""
+        _check(lib().dfk_walks_write(self._ctx, None if directory is None else str(directory).encode()))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
