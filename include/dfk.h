@@ -770,6 +770,70 @@ int dfk_walks_fetch(dfk_ctx* ctx, uint64_t* starts, uint64_t* ee_starts, uint32_
                     uint64_t* n_bases);
 int dfk_walks_write(dfk_ctx* ctx, const char* dir);
 
+/* ---- the second closer's stack consensus: Stackster's two stacks per pair, their Consensus1 with QUALCAP, the MIN_FLAT zeroing and the
+ * conflicting columns per offset (10X/Stackster.cc:396-489, :546-563; ReadStack.cc's Trim, Reverse, Consensus1 with qualities) ----
+ * For a pair where both walks placed an entry (a.stack.walks: status 0 and placed > 0 on both sides) Stackster builds a stack a side from
+ * the placed entries -- row i the read oriented and lowered as the walk saw it, at offset start -- trims it to its last 400 columns,
+ * reverses side 1, and takes Consensus1( con, conq, 100 ) of each: per column four double sums added in row order (0.1 for Q0, 0.2 for
+ * Q1 and Q2, q otherwise), con the base of the greatest ( sum, id ) pair (base 3 where nothing covers), conq = min( 100, int( round(
+ * val(0) - val(1) ) ) ), zeroed where val(1) > 100 and two rows or more of quality >= 30 show the second base.  conq is then zeroed
+ * over every run of 10 equal bases or more of con.  An offset in [-n2, n1) between the two is allowed while fewer than 10 columns have
+ * conq 100 on both sides and different bases; the count is kept for every offset.  No stack is stored.  Every other pair has two
+ * elements of 0 rows and 0 columns and no conflict entries.  The rule, the plan and the file's layout: csrc/dfk_scons.h.
+ *   dfk_scons_build   works from the context's latest dfk_walks_build* result; the read arguments are the reads the walks were made
+ *                     from with their PQVec qualities, checked as dfk_cons_build checks them.  DFK_E_STATE without a walks result.
+ *   dfk_scons_build_arrays  the same stage on host arrays: the walks in dfk_walks_fetch's forms -- starts [2 * n_pairs + 1], records (8
+ *                     u32 a walk), the placed records (16 bytes each) -- and the reads; stacks_per_batch 0 = what fits; with a dir
+ *                     the file is written there.
+ *   DFK_E_ARG for null arguments, starts that fall or disagree with a record's placed, a placed record that names no read or lies
+ *   2^30 columns away, an M that is not the maximum of start + len over a yielding side's records; DFK_E_INPUT for offset tables of
+ *   the reads that fall and for a PQVec stream that does not hold its read's length.  A refused call changes nothing: dfk_scons_stats /
+ *   _fetch / _write serve the latest result of either build, hbm_held is as before.
+ *   dfk_scons_stats   out[DFK_SCONS_WORDS]: the counters below
+ *   dfk_scons_fetch   starts ([n_elements + 1] words, or NULL), conflict_first ([n_elements / 2 + 1] words, or NULL), dims (4 u32 an
+ *                     element, or NULL), con and conq (a byte a column each; both or neither), the conflict counts (u16 each); NULL
+ *                     with cap 0 gives the counts alone; a buffer too small DFK_E_ARG.
+ *   dfk_scons_write   into dir (which must exist), whole or not at all.  Little-endian, no byte undefined:
+ *                       a.stack.cons  "DFKSCON1" | u64 n = 2 * n_pairs | (n + 1) x u64 starts, in columns | (n_pairs + 1) x u64 first
+ *                                     conflict entry of each pair | n x 16-byte { u32 rows, u32 rows_kept, i32 M, u32 cols } | con, a
+ *                                     byte a base | conq, a byte each, after the flat pass | the conflict counts, u16 each: n1 + n2 a
+ *                                     yielding pair, the offset's at index offset + n2 | zero bytes to a multiple of 8.  Element
+ *                                     2 pi + s is side s of pair pi. */
+#define DFK_SCONS_WORDS 32
+#define DFK_SCONS_PAIRS 0            /* pairs */
+#define DFK_SCONS_YIELDS 1           /* pairs with entries placed on both sides: the only ones with stacks */
+#define DFK_SCONS_STACKS 2           /* their stacks */
+#define DFK_SCONS_ROWS 3             /* rows: the placed records of those stacks */
+#define DFK_SCONS_ROWS_KEPT 4        /* rows after Trim */
+#define DFK_SCONS_TRIMMED 5          /* stacks with M > 400 */
+#define DFK_SCONS_COLUMNS 6          /* columns of all stacks */
+#define DFK_SCONS_CELLS 7            /* defined cells added to a sum */
+#define DFK_SCONS_CAPPED 8           /* columns whose int( round( val(0) - val(1) ) ) was 100 or more */
+#define DFK_SCONS_RECOUNT 9          /* columns the recount zeroed: val(1) > 100, two rows of quality >= 30 on id(1) */
+#define DFK_SCONS_FLAT 10            /* columns in runs of 10 equal bases or more: zeroed as flat */
+#define DFK_SCONS_ALLOWED 11         /* offsets with fewer than 10 conflicting columns, */
+#define DFK_SCONS_DISALLOWED 12      /* and the others */
+#define DFK_SCONS_LIVE 13            /* rows whose span meets their stack's window */
+#define DFK_SCONS_DECODED 14         /* reads gathered, decoded and lowered, a read once a batch */
+#define DFK_SCONS_BATCHES 15         /* batches of stacks */
+#define DFK_SCONS_RANGES 16          /* ranges of pairs */
+#define DFK_SCONS_US 17              /* microseconds: the build call, */
+#define DFK_SCONS_US_COPY 18         /* the live rows and the gather on the host and the copies, */
+#define DFK_SCONS_US_DECODE 19       /* decode and lowering, */
+#define DFK_SCONS_US_CONS 20         /* the consensus kernel, */
+#define DFK_SCONS_US_FLAT 21         /* the flat pass, */
+#define DFK_SCONS_US_CONFLICTS 22    /* the conflicts */
+#define DFK_SCONS_SUM 23             /* sum and xor over positions i of h(i, value) (k_digest_seq, salt 0x5C05): the dims as u32 words, con, conq, the conflict counts */
+#define DFK_SCONS_XOR 24
+int dfk_scons_build(dfk_ctx* ctx, const uint8_t* packed_bases, const uint64_t* base_off /* or NULL: dense */, const uint32_t* read_len, const uint8_t* pq, const uint64_t* pq_off, uint64_t n_reads);
+int dfk_scons_build_arrays(dfk_ctx* ctx, const uint64_t* starts /* [2 * n_pairs + 1] */, const uint32_t* records /* 8 a walk */, const void* placed, uint64_t n_pairs, const uint8_t* packed_bases,
+                           const uint64_t* base_off, const uint32_t* read_len, const uint8_t* pq, const uint64_t* pq_off, uint64_t n_reads, uint64_t stacks_per_batch /* 0 = what fits */,
+                           const char* dir /* NULL = no file */);
+int dfk_scons_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_SCONS_WORDS] */);
+int dfk_scons_fetch(dfk_ctx* ctx, uint64_t* starts, uint64_t* conflict_first, uint32_t* dims, uint64_t* n_elements, uint8_t* con, uint8_t* conq, uint64_t cols_cap, uint64_t* n_cols, uint16_t* counts,
+                    uint64_t counts_cap, uint64_t* n_counts);
+int dfk_scons_write(dfk_ctx* ctx, const char* dir);
+
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).
  * dfk_paths_digest  fills out[DFK_CHECK_WORDS] with digests that depend on the CONTENT of a.paths, a.paths.inv, a.countsb and

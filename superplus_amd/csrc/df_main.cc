@@ -552,7 +552,7 @@ int main(int argc, char** argv)
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
         {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
-        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}, {"WALKS", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}, {"WALKS", "False"}, {"SCONS", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -604,6 +604,11 @@ int main(int argc, char** argv)
     // edges' bases and the reads with their qualities (the maps stay, as for CONS=True); like HOPS=True, which CLOSER=True needs, it runs on one GPU only
     if (truthy(a["WALKS"]) && !truthy(a["CLOSER"])) give_up("WALKS=True needs CLOSER=True: a walk runs through the read set the closers made for its pair");
     const bool want_walks = truthy(a["WALKS"]);
+
+    // SCONS=True (Stackster's stack consensus per pair, Stackster.cc:396-489 and :546-563, a.<K>/a.stack.cons) works from the walks and the reads with their
+    // qualities; it runs where WALKS=True runs
+    if (truthy(a["SCONS"]) && !want_walks) give_up("SCONS=True needs WALKS=True: the stacks are built from the entries the walks placed");
+    const bool want_scons = truthy(a["SCONS"]);
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -1123,6 +1128,19 @@ int main(int argc, char** argv)
                                    (unsigned long long)ws[DFK_WALKS_STEPS], (unsigned long long)ws[DFK_WALKS_DUP_STEPS], (unsigned long long)ws[DFK_WALKS_PAST_EDGE], (unsigned long long)ws[DFK_WALKS_SIDE0_EMPTY],
                                    (unsigned long long)ws[DFK_WALKS_SIDE1_EMPTY], (unsigned long long)ws[DFK_WALKS_SHORT], (unsigned long long)ws[DFK_WALKS_TRIMMED], (unsigned long long)ws[DFK_WALKS_YIELDS],
                                    (unsigned long long)ws[DFK_WALKS_LIVE_MAX], (unsigned long long)ws[DFK_WALKS_HOST_ROUTE], (unsigned long long)ws[DFK_WALKS_BATCHES], (unsigned long long)ws[DFK_WALKS_RANGES]);
+                            if (want_scons) {                                   // Stackster's stack consensus per pair (Stackster.cc:396-489, :546-563): a.<K>/a.stack.cons, after a.stack.walks
+                                uint64_t ss[DFK_SCONS_WORDS] = {};
+                                const int src = fast ? dfk_scons_build(ctx, h_packed + (n_reads ? ld64(h_boff) : 0), nullptr, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, n_reads)      // (dense: validated at load)
+                                                     : dfk_scons_build(ctx, h_packed, (const uint64_t*)h_boff, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, n_reads);
+                                if (src || dfk_scons_write(ctx, dir.c_str()) || dfk_scons_stats(ctx, ss)) throw std::runtime_error(dfk_last_error());
+                                printf("DF_SCONS {\"pairs\": %llu, \"yields\": %llu, \"stacks\": %llu, \"rows\": %llu, \"rows_kept\": %llu, \"trimmed\": %llu, \"columns\": %llu, \"a.stack.cons\": \"%016llx%016llx\", "
+                                       "\"cells\": %llu, \"capped\": %llu, \"recount\": %llu, \"flat\": %llu, \"allowed\": %llu, \"disallowed\": %llu, \"batches\": %llu, \"ranges\": %llu}\n",
+                                       (unsigned long long)ss[DFK_SCONS_PAIRS], (unsigned long long)ss[DFK_SCONS_YIELDS], (unsigned long long)ss[DFK_SCONS_STACKS], (unsigned long long)ss[DFK_SCONS_ROWS],
+                                       (unsigned long long)ss[DFK_SCONS_ROWS_KEPT], (unsigned long long)ss[DFK_SCONS_TRIMMED], (unsigned long long)ss[DFK_SCONS_COLUMNS], (unsigned long long)ss[DFK_SCONS_SUM],
+                                       (unsigned long long)ss[DFK_SCONS_XOR], (unsigned long long)ss[DFK_SCONS_CELLS], (unsigned long long)ss[DFK_SCONS_CAPPED], (unsigned long long)ss[DFK_SCONS_RECOUNT],
+                                       (unsigned long long)ss[DFK_SCONS_FLAT], (unsigned long long)ss[DFK_SCONS_ALLOWED], (unsigned long long)ss[DFK_SCONS_DISALLOWED], (unsigned long long)ss[DFK_SCONS_BATCHES],
+                                       (unsigned long long)ss[DFK_SCONS_RANGES]);
+                            }
                         }
                     }
                 }

@@ -53,6 +53,8 @@ struct HostGraph {
     void (*closures_free)(struct ClosuresResult*) = nullptr;
     struct WalksResult* walks = nullptr;                             // the latest dfk_walks_build*'s result (dfk_walks.inc)
     void (*walks_free)(struct WalksResult*) = nullptr;
+    struct SconsResult* scons = nullptr;                             // the latest dfk_scons_build*'s result (dfk_scons.inc)
+    void (*scons_free)(struct SconsResult*) = nullptr;
     ~HostGraph()
     {
         if (paths && paths_free) paths_free(paths);
@@ -64,6 +66,7 @@ struct HostGraph {
         if (offsets && offsets_free) offsets_free(offsets);
         if (closures && closures_free) closures_free(closures);
         if (walks && walks_free) walks_free(walks);
+        if (scons && scons_free) scons_free(scons);
     }
 };
 

@@ -39,6 +39,7 @@ EXPORTS = [
     "dfk_offsets_build", "dfk_offsets_build_arrays", "dfk_offsets_stats", "dfk_offsets_fetch", "dfk_offsets_write",
     "dfk_closures_build", "dfk_closures_build_arrays", "dfk_closures_stats", "dfk_closures_fetch", "dfk_closures_write",
     "dfk_walks_build", "dfk_walks_build_arrays", "dfk_walks_stats", "dfk_walks_fetch", "dfk_walks_write",
+    "dfk_scons_build", "dfk_scons_build_arrays", "dfk_scons_stats", "dfk_scons_fetch", "dfk_scons_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -85,6 +86,11 @@ WALKS = ["pairs", "walks", "entries", "placed", "ee", "longest", "dup_steps", "s
          "host_route", "verified", "collisions", "kmers", "decoded", "batches", "ranges", "us", "us_copy", "us_decode", "us_sort", "us_walk", "sum", "xor"]
 WALKS_FILE = "a.stack.walks"
 WALKS_PLACED = np.dtype([("id", "<i8"), ("start", "<i4"), ("fw", "<u4")])
+# dfk_scons_stats' words (include/dfk.h, DFK_SCONS_*)
+SCONS_WORDS = 32
+SCONS = ["pairs", "yields", "stacks", "rows", "rows_kept", "trimmed", "columns", "cells", "capped", "recount", "flat", "allowed", "disallowed", "live", "decoded", "batches", "ranges",
+         "us", "us_copy", "us_decode", "us_cons", "us_flat", "us_conflicts", "sum", "xor"]
+SCONS_FILE = "a.stack.cons"
 # dfk_adj_outcome's codes (include/dfk.h, DFK_ADJ_*)
 ADJ_OUTCOMES = ["not applicable", "used", "discarded: guess too low", "discarded: list problem", "no block", "dropped for an allocation",
                 "switched off"]
@@ -717,6 +723,49 @@ class Dfk:
     def walks_write(self, directory):
         """dfk_walks_write: a.stack.walks into `directory` (which must exist)."""
         _check(lib().dfk_walks_write(self._ctx, None if directory is None else str(directory).encode()))
+
+    def scons_build(self, packed, base_off, read_len, pq_bytes, pq_off):
+        """dfk_scons_build: Stackster's stack consensus per pair, after walks_build; the reads are the ones the walks were made from with
+        their PQVec qualities.  Returns scons_stats()."""
+        n = 0 if read_len is None else len(read_len)
+        packed, read_len, pq_bytes = (None if x is None else np.ascontiguousarray(x, t) for x, t in ((packed, np.uint8), (read_len, np.uint32), (pq_bytes, np.uint8)))
+        base_off, pq_off = (None if x is None else np.ascontiguousarray(x, np.uint64) for x in (base_off, pq_off))
+        _check(lib().dfk_scons_build(self._ctx, _p(packed), _p(base_off), _p(read_len), _p(pq_bytes), _p(pq_off), C.c_uint64(n)))
+        return self.scons_stats()
+
+    def scons_build_arrays(self, a, stacks_per_batch=0, directory=None, **change):
+        """dfk_scons_build_arrays: the same stage on arrays.  a: dict(starts uint64[2 p + 1], records uint32[2 p, 8], placed WALKS_PLACED[]
+        (walks_fetch's forms), read_packed, read_off, read_len, pq, pq_off); a key in `change` replaces one (None: a NULL pointer).  With
+        a directory a.stack.cons is written there.  Returns scons_stats()."""
+        a = dict(a); a.update(change)
+        kinds = dict(starts=np.uint64, records=np.uint32, placed=WALKS_PLACED, read_packed=np.uint8, read_off=np.uint64, read_len=np.uint32, pq=np.uint8, pq_off=np.uint64)
+        n = {k: (0 if a[k] is None else len(a[k])) for k in kinds}
+        # (an empty array still has an address: NULL is for what is left out on purpose)
+        v = {k: None if a[k] is None else np.ascontiguousarray(a[k] if len(a[k]) else np.zeros(1, t), t) for k, t in kinds.items()}
+        _check(lib().dfk_scons_build_arrays(self._ctx, _p(v["starts"]), _p(v["records"]), _p(v["placed"]), C.c_uint64((n["starts"] - 1) // 2 if n["starts"] else n["records"] // 2), _p(v["read_packed"]), _p(v["read_off"]), _p(v["read_len"]),
+                                            _p(v["pq"]), _p(v["pq_off"]), C.c_uint64(n["read_len"]), C.c_uint64(stacks_per_batch), None if directory is None else str(directory).encode()))
+        return self.scons_stats()
+
+    def scons_stats(self):
+        """dfk_scons_stats: {counter: value} -- pairs, yielding pairs, stacks, rows, rows kept, trimmed stacks, columns, cells, columns capped,
+        recounted and flat, offsets allowed and disallowed, live rows, decoded reads, batches, ranges, times, digest."""
+        out = (C.c_uint64 * SCONS_WORDS)()
+        _check(lib().dfk_scons_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(SCONS)}
+
+    def scons_fetch(self):
+        """dfk_scons_fetch: dict(starts uint64[n + 1], conflict_first uint64[n / 2 + 1], dims uint32[n, 4] (rows, rows_kept, M, cols), con
+        uint8[], conq uint8[], counts uint16[])."""
+        n, nc, nk = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().dfk_scons_fetch(self._ctx, None, None, None, C.byref(n), None, None, C.c_uint64(0), C.byref(nc), None, C.c_uint64(0), C.byref(nk)))
+        starts, cfirst = np.zeros(n.value + 1, np.uint64), np.zeros(n.value // 2 + 1, np.uint64)
+        dims, con, conq, counts = np.zeros((max(1, n.value), 4), np.uint32), np.zeros(max(1, nc.value), np.uint8), np.zeros(max(1, nc.value), np.uint8), np.zeros(max(1, nk.value), np.uint16)
+        _check(lib().dfk_scons_fetch(self._ctx, _p(starts), _p(cfirst), _p(dims), C.byref(n), _p(con), _p(conq), C.c_uint64(nc.value), C.byref(nc), _p(counts), C.c_uint64(nk.value), C.byref(nk)))
+        return dict(starts=starts, conflict_first=cfirst, dims=dims[: n.value], con=con[: nc.value], conq=conq[: nc.value], counts=counts[: nk.value])
+
+    def scons_write(self, directory):
+        """dfk_scons_write: a.stack.cons into `directory` (which must exist)."""
+        _check(lib().dfk_scons_write(self._ctx, None if directory is None else str(directory).encode()))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
