@@ -834,6 +834,74 @@ int dfk_scons_fetch(dfk_ctx* ctx, uint64_t* starts, uint64_t* conflict_first, ui
                     uint64_t counts_cap, uint64_t* n_counts);
 int dfk_scons_write(dfk_ctx* ctx, const char* dir);
 
+/* ---- Stackster's stack offsets per pair: the rows of one stack searched for the acceptable 8-mers of the other stack's consensus, the
+ * bits of every ( row, offset ), the offsets within 20 bits of the best (10X/Stackster.cc:461-645) ----
+ * For s in 0, 1 an 8-mer of side s's con is acceptable when neither half is flat and it holds three different bases; every row of the
+ * other stack whose 8 cells at l are all defined (lowered quality below 128) and equal an acceptable 8-mer at j proposes offset = ( s
+ * == 0 ? j - l : l - j ).  A ( row, offset ) counts once a side, and only where a.stack.cons' conflict count of the offset is below 10.
+ * Its bits: over the overlap of con and the stack at that offset the windows of 20 columns or more whose two end cells the row defines,
+ * minp = Min T[n][mismatches] over the table of log binomial sums (dfk_offsets'), bits = -minp * 10.0 / 6.0; a result with 20 bits or
+ * more.  Per distinct offset the greatest bits; an offset is kept within 20.0 of the pair's best; a pair is closable with 1 to 3 kept
+ * offsets.  Every pair that does not yield has no record.  The rule, the plan and the file's layout: csrc/dfk_soffsets.h.
+ *   dfk_soffsets_build   works from the context's latest dfk_walks_build* AND dfk_scons_build results; the read arguments are the reads
+ *                     they were made from.  DFK_E_STATE without both, or when the consensus was not made by dfk_scons_build from
+ *                     these walks.
+ *   dfk_soffsets_build_arrays  the same stage on host arrays and without a graph: the walks in dfk_walks_fetch's forms, the reads, the
+ *                     stack consensus in dfk_scons_fetch's forms -- cons_starts [2 * n_pairs + 1], dims (4 u32 an element), con,
+ *                     conq, conflict_first [n_pairs + 1], counts --; rows_per_batch 0 = what fits, else whole pairs while their live
+ *                     rows stay at it (one pair at least); with a dir the file is written there.
+ *   DFK_E_ARG for what dfk_scons_build_arrays refuses and for consensus starts that do not begin at 0 or fall, a base above 3, an
+ *   element wider than 400 or not as wide as its dims and its walk's M say, a counts table that is not n1 + n2 long for a yielding
+ *   pair (0 for another).  A refused call changes nothing: dfk_soffsets_stats / _fetch / _write serve the latest result of either
+ *   build, hbm_held is as before.
+ *   dfk_soffsets_stats   out[DFK_SOFFSETS_WORDS]: the counters below
+ *   dfk_soffsets_fetch   starts ([n_pairs + 1] words, or NULL), words (4 u32 a pair, or NULL), the records (24 bytes each); NULL with
+ *                     cap 0 gives the counts alone; a buffer too small DFK_E_ARG.
+ *   dfk_soffsets_write   into dir (which must exist), whole or not at all.  Little-endian, no byte undefined:
+ *                       a.stack.offsets  "DFKSOFF1" | u64 n_pairs | (n_pairs + 1) x u64 starts, in records | n_pairs x 16-byte { u32
+ *                                     seen, u32 results, u32 kept, u32 closable } | 24-byte records { i32 offset, u32 results, f64
+ *                                     best_bits, u32 state, u32 0 }, one per distinct offset with a result, ascending; state 0 kept, 1
+ *                                     dropped. */
+#define DFK_SOFFSETS_WORDS 32
+#define DFK_SOFFSETS_PAIRS 0         /* pairs */
+#define DFK_SOFFSETS_YIELDS 1        /* pairs with entries placed on both sides: the only ones searched */
+#define DFK_SOFFSETS_ROWS 2          /* rows searched: the rows their stacks kept */
+#define DFK_SOFFSETS_KMERS 3         /* row 8-mers with all 8 cells defined */
+#define DFK_SOFFSETS_ACCEPTABLE 4    /* acceptable 8-mers of con, both sides */
+#define DFK_SOFFSETS_HITS 5          /* ( row 8-mer, acceptable con 8-mer ) that are equal */
+#define DFK_SOFFSETS_SEEN 6          /* candidates ( s, row, offset ) seen */
+#define DFK_SOFFSETS_DISALLOWED 7    /* hits skipped because their offset has 10 conflicting columns or more */
+#define DFK_SOFFSETS_LOOKUPS 8       /* look-ups in the table of log binomial sums */
+#define DFK_SOFFSETS_RESULTS 9       /* candidates with 20 bits or more */
+#define DFK_SOFFSETS_OFFSETS 10      /* distinct offsets with a result: the records */
+#define DFK_SOFFSETS_KEPT 11         /* of them kept, */
+#define DFK_SOFFSETS_DROPPED 12      /* and dropped as more than 20 bits below the pair's best */
+#define DFK_SOFFSETS_PAIRS_0 13      /* pairs with no kept offset, */
+#define DFK_SOFFSETS_PAIRS_1 14      /* one, */
+#define DFK_SOFFSETS_PAIRS_2 15      /* two, */
+#define DFK_SOFFSETS_PAIRS_3 16      /* three, */
+#define DFK_SOFFSETS_PAIRS_MORE 17   /* more */
+#define DFK_SOFFSETS_CLOSABLE 18     /* pairs with one to three kept offsets */
+#define DFK_SOFFSETS_LIVE 19         /* rows whose span meets their stack's window */
+#define DFK_SOFFSETS_DECODED 20      /* reads gathered, decoded and lowered, a read once a batch */
+#define DFK_SOFFSETS_BATCHES 21      /* batches of pairs */
+#define DFK_SOFFSETS_RANGES 22       /* ranges of pairs */
+#define DFK_SOFFSETS_US 23           /* microseconds: the build call, */
+#define DFK_SOFFSETS_US_COPY 24      /* the live rows and the gather on the host and the copies, */
+#define DFK_SOFFSETS_US_DECODE 25    /* decode and lowering, */
+#define DFK_SOFFSETS_US_SEARCH 26    /* the search kernel, */
+#define DFK_SOFFSETS_US_EMIT 27      /* the scan and the emit */
+#define DFK_SOFFSETS_SUM 28          /* sum and xor over positions i of h(i, value) (k_digest_seq, salt 0x50FF): the per-pair words, then the records as u32 words */
+#define DFK_SOFFSETS_XOR 29
+int dfk_soffsets_build(dfk_ctx* ctx, const uint8_t* packed_bases, const uint64_t* base_off /* or NULL: dense */, const uint32_t* read_len, const uint8_t* pq, const uint64_t* pq_off, uint64_t n_reads);
+int dfk_soffsets_build_arrays(dfk_ctx* ctx, const uint64_t* starts /* [2 * n_pairs + 1] */, const uint32_t* records /* 8 a walk */, const void* placed, uint64_t n_pairs, const uint8_t* packed_bases,
+                              const uint64_t* base_off, const uint32_t* read_len, const uint8_t* pq, const uint64_t* pq_off, uint64_t n_reads, const uint64_t* cons_starts /* [2 * n_pairs + 1] */,
+                              const uint32_t* dims /* 4 an element */, const uint8_t* con, const uint8_t* conq, const uint64_t* conflict_first /* [n_pairs + 1] */, const uint16_t* counts,
+                              uint64_t rows_per_batch /* 0 = what fits */, const char* dir /* NULL = no file */);
+int dfk_soffsets_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_SOFFSETS_WORDS] */);
+int dfk_soffsets_fetch(dfk_ctx* ctx, uint64_t* starts, uint32_t* words, uint64_t* n_pairs, void* records, uint64_t records_cap, uint64_t* n_records);
+int dfk_soffsets_write(dfk_ctx* ctx, const char* dir);
+
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).
  * dfk_paths_digest  fills out[DFK_CHECK_WORDS] with digests that depend on the CONTENT of a.paths, a.paths.inv, a.countsb and

@@ -552,7 +552,7 @@ int main(int argc, char** argv)
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
         {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
-        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}, {"WALKS", "False"}, {"SCONS", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}, {"WALKS", "False"}, {"SCONS", "False"}, {"SOFFSETS", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -609,6 +609,11 @@ int main(int argc, char** argv)
     // qualities; it runs where WALKS=True runs
     if (truthy(a["SCONS"]) && !want_walks) give_up("SCONS=True needs WALKS=True: the stacks are built from the entries the walks placed");
     const bool want_scons = truthy(a["SCONS"]);
+
+    // SOFFSETS=True (Stackster's stack offsets per pair, Stackster.cc:461-645, a.<K>/a.stack.offsets) works from the walks, their stack consensus and the reads
+    // with their qualities; it runs where SCONS=True runs
+    if (truthy(a["SOFFSETS"]) && !want_scons) give_up("SOFFSETS=True needs SCONS=True: a stack's rows are searched for the 8-mers of the other stack's consensus");
+    const bool want_soffsets = truthy(a["SOFFSETS"]);
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -1140,6 +1145,21 @@ int main(int argc, char** argv)
                                        (unsigned long long)ss[DFK_SCONS_XOR], (unsigned long long)ss[DFK_SCONS_CELLS], (unsigned long long)ss[DFK_SCONS_CAPPED], (unsigned long long)ss[DFK_SCONS_RECOUNT],
                                        (unsigned long long)ss[DFK_SCONS_FLAT], (unsigned long long)ss[DFK_SCONS_ALLOWED], (unsigned long long)ss[DFK_SCONS_DISALLOWED], (unsigned long long)ss[DFK_SCONS_BATCHES],
                                        (unsigned long long)ss[DFK_SCONS_RANGES]);
+                                if (want_soffsets) {                            // Stackster's stack offsets per pair (Stackster.cc:461-645): a.<K>/a.stack.offsets, after a.stack.cons
+                                    uint64_t so[DFK_SOFFSETS_WORDS] = {};
+                                    const int orc = fast ? dfk_soffsets_build(ctx, h_packed + (n_reads ? ld64(h_boff) : 0), nullptr, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, n_reads)      // (dense: validated at load)
+                                                         : dfk_soffsets_build(ctx, h_packed, (const uint64_t*)h_boff, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, n_reads);
+                                    if (orc || dfk_soffsets_write(ctx, dir.c_str()) || dfk_soffsets_stats(ctx, so)) throw std::runtime_error(dfk_last_error());
+                                    printf("DF_SOFFSETS {\"pairs\": %llu, \"yields\": %llu, \"rows\": %llu, \"kmers\": %llu, \"acceptable\": %llu, \"hits\": %llu, \"seen\": %llu, \"disallowed\": %llu, \"lookups\": %llu, "
+                                           "\"results\": %llu, \"offsets\": %llu, \"kept\": %llu, \"dropped\": %llu, \"pairs_0\": %llu, \"pairs_1\": %llu, \"pairs_2\": %llu, \"pairs_3\": %llu, \"pairs_more\": %llu, "
+                                           "\"closable\": %llu, \"a.stack.offsets\": \"%016llx%016llx\", \"batches\": %llu, \"ranges\": %llu}\n",
+                                           (unsigned long long)so[DFK_SOFFSETS_PAIRS], (unsigned long long)so[DFK_SOFFSETS_YIELDS], (unsigned long long)so[DFK_SOFFSETS_ROWS], (unsigned long long)so[DFK_SOFFSETS_KMERS],
+                                           (unsigned long long)so[DFK_SOFFSETS_ACCEPTABLE], (unsigned long long)so[DFK_SOFFSETS_HITS], (unsigned long long)so[DFK_SOFFSETS_SEEN], (unsigned long long)so[DFK_SOFFSETS_DISALLOWED],
+                                           (unsigned long long)so[DFK_SOFFSETS_LOOKUPS], (unsigned long long)so[DFK_SOFFSETS_RESULTS], (unsigned long long)so[DFK_SOFFSETS_OFFSETS], (unsigned long long)so[DFK_SOFFSETS_KEPT],
+                                           (unsigned long long)so[DFK_SOFFSETS_DROPPED], (unsigned long long)so[DFK_SOFFSETS_PAIRS_0], (unsigned long long)so[DFK_SOFFSETS_PAIRS_1], (unsigned long long)so[DFK_SOFFSETS_PAIRS_2],
+                                           (unsigned long long)so[DFK_SOFFSETS_PAIRS_3], (unsigned long long)so[DFK_SOFFSETS_PAIRS_MORE], (unsigned long long)so[DFK_SOFFSETS_CLOSABLE], (unsigned long long)so[DFK_SOFFSETS_SUM],
+                                           (unsigned long long)so[DFK_SOFFSETS_XOR], (unsigned long long)so[DFK_SOFFSETS_BATCHES], (unsigned long long)so[DFK_SOFFSETS_RANGES]);
+                                }
                             }
                         }
                     }

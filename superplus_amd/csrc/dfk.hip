@@ -2286,5 +2286,6 @@ int dfk_adj_outcome(dfk_ctx* c, uint32_t* outcome, uint64_t* slots)
 #include "dfk_closures.inc"
 #include "dfk_walks.inc"
 #include "dfk_scons.inc"
+#include "dfk_soffsets.inc"
 #include "dfk_paths_shard.inc"
 #include "dfk_pbf.inc"

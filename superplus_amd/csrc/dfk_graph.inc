@@ -55,6 +55,8 @@ struct HostGraph {
     void (*walks_free)(struct WalksResult*) = nullptr;
     struct SconsResult* scons = nullptr;                             // the latest dfk_scons_build*'s result (dfk_scons.inc)
     void (*scons_free)(struct SconsResult*) = nullptr;
+    struct SoffsetsResult* soffsets = nullptr;                       // the latest dfk_soffsets_build*'s result (dfk_soffsets.inc)
+    void (*soffsets_free)(struct SoffsetsResult*) = nullptr;
     ~HostGraph()
     {
         if (paths && paths_free) paths_free(paths);
@@ -67,6 +69,7 @@ struct HostGraph {
         if (closures && closures_free) closures_free(closures);
         if (walks && walks_free) walks_free(walks);
         if (scons && scons_free) scons_free(scons);
+        if (soffsets && soffsets_free) soffsets_free(soffsets);
     }
 };
 

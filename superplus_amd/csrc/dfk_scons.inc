@@ -17,6 +17,7 @@ struct SconsResult {
     std::vector<uint8_t> con, conq;
     std::vector<uint16_t> counts;
     uint64_t stats[DFK_SCONS_WORDS] = {};
+    uint64_t walks_serial = 0;                    // dfk_scons_build: the walks it was made from (0: from arrays); dfk_soffsets_build asks
 };
 void scons_result_free(SconsResult* r) { delete r; }
 
@@ -280,6 +281,7 @@ int dfk_scons_build(dfk_ctx* c, const uint8_t* packed, const uint64_t* base_off,
     const SconsSource S{W->recs.size() / 2, W->starts.data(), W->recs.empty() ? &no_rec : W->recs.data(), W->locs.empty() ? &no_loc : W->locs.data(), &reads, pq, pq_off};
     std::unique_ptr<SconsResult> R(new SconsResult);
     if (int rc = scons_build(c, S, 0, R.get())) return rc;                                  // (refused: the earlier result is still served)
+    R->walks_serial = W->serial;
     scons_keep(c, R.release());
     return 0;
     });

@@ -18,6 +18,7 @@ struct WalksResult {
     std::vector<uint8_t> ee;                      // a byte a base
     uint64_t n_reads = 0;                         // the reads it was made from: dfk_scons_build asks for as many
     uint64_t stats[DFK_WALKS_WORDS] = {};
+    uint64_t serial = 0;                          // which build made it: dfk_scons_build notes it, dfk_soffsets_build asks for the same
 };
 void walks_result_free(WalksResult* r) { delete r; }
 
@@ -97,7 +98,7 @@ int walks_build(dfk_ctx* c, const WalksSource& S, const int32_t* pairs, uint64_t
     CnTimes times;
     float ms_lower = 0, ms_sort = 0, ms_walk = 0;
     uint64_t n_batches = 0, n_ranges = 0, n_decoded = 0, n_items_all = 0, n_host = 0, n_steps = 0, live_sum = 0, live_max = 0, n_verified = 0, n_collisions = 0, h_dg[8] = {};
-    R->starts.assign(1, 0); R->ee_starts.assign(1, 0); R->n_reads = N;
+    R->starts.assign(1, 0); R->ee_starts.assign(1, 0); R->n_reads = N; R->serial = cons_next_serial();
     auto len_of = [&](uint64_t id, uint32_t* len) { return host_read(c, len, S.rd->len + id, 4); };
     auto body = [&]() -> int {
         int rc;

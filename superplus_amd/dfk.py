@@ -40,6 +40,7 @@ EXPORTS = [
     "dfk_closures_build", "dfk_closures_build_arrays", "dfk_closures_stats", "dfk_closures_fetch", "dfk_closures_write",
     "dfk_walks_build", "dfk_walks_build_arrays", "dfk_walks_stats", "dfk_walks_fetch", "dfk_walks_write",
     "dfk_scons_build", "dfk_scons_build_arrays", "dfk_scons_stats", "dfk_scons_fetch", "dfk_scons_write",
+    "dfk_soffsets_build", "dfk_soffsets_build_arrays", "dfk_soffsets_stats", "dfk_soffsets_fetch", "dfk_soffsets_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -91,6 +92,12 @@ SCONS_WORDS = 32
 SCONS = ["pairs", "yields", "stacks", "rows", "rows_kept", "trimmed", "columns", "cells", "capped", "recount", "flat", "allowed", "disallowed", "live", "decoded", "batches", "ranges",
          "us", "us_copy", "us_decode", "us_cons", "us_flat", "us_conflicts", "sum", "xor"]
 SCONS_FILE = "a.stack.cons"
+# dfk_soffsets_stats' words (include/dfk.h, DFK_SOFFSETS_*)
+SOFFSETS_WORDS = 32
+SOFFSETS = ["pairs", "yields", "rows", "kmers", "acceptable", "hits", "seen", "disallowed", "lookups", "results", "offsets", "kept", "dropped", "pairs_0", "pairs_1", "pairs_2", "pairs_3",
+            "pairs_more", "closable", "live", "decoded", "batches", "ranges", "us", "us_copy", "us_decode", "us_search", "us_emit", "sum", "xor"]
+SOFFSETS_FILE = "a.stack.offsets"
+SOFFSETS_RECORD = np.dtype([("offset", "<i4"), ("results", "<u4"), ("best_bits", "<f8"), ("state", "<u4"), ("zero", "<u4")])
 # dfk_adj_outcome's codes (include/dfk.h, DFK_ADJ_*)
 ADJ_OUTCOMES = ["not applicable", "used", "discarded: guess too low", "discarded: list problem", "no block", "dropped for an allocation",
                 "switched off"]
@@ -766,6 +773,50 @@ class Dfk:
     def scons_write(self, directory):
         """dfk_scons_write: a.stack.cons into `directory` (which must exist)."""
         _check(lib().dfk_scons_write(self._ctx, None if directory is None else str(directory).encode()))
+
+    def soffsets_build(self, packed, base_off, read_len, pq_bytes, pq_off):
+        """dfk_soffsets_build: Stackster's stack offsets per pair, after walks_build and scons_build; the reads are the ones they were
+        made from with their PQVec qualities.  Returns soffsets_stats()."""
+        n = 0 if read_len is None else len(read_len)
+        packed, read_len, pq_bytes = (None if x is None else np.ascontiguousarray(x, t) for x, t in ((packed, np.uint8), (read_len, np.uint32), (pq_bytes, np.uint8)))
+        base_off, pq_off = (None if x is None else np.ascontiguousarray(x, np.uint64) for x in (base_off, pq_off))
+        _check(lib().dfk_soffsets_build(self._ctx, _p(packed), _p(base_off), _p(read_len), _p(pq_bytes), _p(pq_off), C.c_uint64(n)))
+        return self.soffsets_stats()
+
+    def soffsets_build_arrays(self, a, rows_per_batch=0, directory=None, **change):
+        """dfk_soffsets_build_arrays: the same stage on arrays.  a: scons_build_arrays' dict and, in scons_fetch's forms, cons_starts
+        uint64[2 p + 1], dims uint32[2 p, 4], con uint8[], conq uint8[], conflict_first uint64[p + 1], counts uint16[]; a key in `change`
+        replaces one (None: a NULL pointer).  With a directory a.stack.offsets is written there.  Returns soffsets_stats()."""
+        a = dict(a); a.update(change)
+        kinds = dict(starts=np.uint64, records=np.uint32, placed=WALKS_PLACED, read_packed=np.uint8, read_off=np.uint64, read_len=np.uint32, pq=np.uint8, pq_off=np.uint64,
+                     cons_starts=np.uint64, dims=np.uint32, con=np.uint8, conq=np.uint8, conflict_first=np.uint64, counts=np.uint16)
+        n = {k: (0 if a[k] is None else len(a[k])) for k in kinds}
+        # (an empty array still has an address: NULL is for what is left out on purpose)
+        v = {k: None if a[k] is None else np.ascontiguousarray(a[k] if len(a[k]) else np.zeros(1, t), t) for k, t in kinds.items()}
+        _check(lib().dfk_soffsets_build_arrays(self._ctx, _p(v["starts"]), _p(v["records"]), _p(v["placed"]), C.c_uint64((n["starts"] - 1) // 2 if n["starts"] else n["records"] // 2), _p(v["read_packed"]), _p(v["read_off"]),
+                                               _p(v["read_len"]), _p(v["pq"]), _p(v["pq_off"]), C.c_uint64(n["read_len"]), _p(v["cons_starts"]), _p(v["dims"]), _p(v["con"]), _p(v["conq"]), _p(v["conflict_first"]),
+                                               _p(v["counts"]), C.c_uint64(rows_per_batch), None if directory is None else str(directory).encode()))
+        return self.soffsets_stats()
+
+    def soffsets_stats(self):
+        """dfk_soffsets_stats: {counter: value} -- pairs, yielding pairs, rows searched, row 8-mers defined, acceptable con 8-mers, hits,
+        candidates seen, hits skipped as disallowed, look-ups, results, distinct offsets, kept, dropped, pairs by kept offsets, closable pairs,
+        live rows, decoded reads, batches, ranges, times, digest."""
+        out = (C.c_uint64 * SOFFSETS_WORDS)()
+        _check(lib().dfk_soffsets_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(SOFFSETS)}
+
+    def soffsets_fetch(self):
+        """dfk_soffsets_fetch: dict(starts uint64[n + 1], words uint32[n, 4] (seen, results, kept, closable), records SOFFSETS_RECORD[])."""
+        n, nr = C.c_uint64(), C.c_uint64()
+        _check(lib().dfk_soffsets_fetch(self._ctx, None, None, C.byref(n), None, C.c_uint64(0), C.byref(nr)))
+        starts, words, recs = np.zeros(n.value + 1, np.uint64), np.zeros((max(1, n.value), 4), np.uint32), np.zeros(max(1, nr.value), SOFFSETS_RECORD)
+        _check(lib().dfk_soffsets_fetch(self._ctx, _p(starts), _p(words), C.byref(n), _p(recs), C.c_uint64(nr.value), C.byref(nr)))
+        return dict(starts=starts, words=words[: n.value], records=recs[: nr.value])
+
+    def soffsets_write(self, directory):
+        """dfk_soffsets_write: a.stack.offsets into `directory` (which must exist)."""
+        _check(lib().dfk_soffsets_write(self._ctx, None if directory is None else str(directory).encode()))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
