@@ -902,6 +902,73 @@ int dfk_soffsets_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_SOFFSETS_WORDS] */);
 int dfk_soffsets_fetch(dfk_ctx* ctx, uint64_t* starts, uint32_t* words, uint64_t* n_pairs, void* records, uint64_t records_cap, uint64_t* n_records);
 int dfk_soffsets_write(dfk_ctx* ctx, const char* dir);
 
+/* ---- Stackster's closures per pair: the two stacks trimmed to the edges, merged at each kept offset, Consensus1 of the merged stack
+ * (10X/Stackster.cc:712-757; ReadStack.cc's Trim, Merge and Consensus1 with qualities) ----
+ * A pair with one to three kept offsets (the state-0 records of a.stack.offsets) gets one closure per kept offset, ascending; every
+ * other pair none.  At an offset stack 0 is cut to the columns [0, offset + n2) where it is wider, stack 1 to [-offset, n2) where the
+ * offset is negative; rows without a defined cell in the kept columns go.  The merged stack is C = offset + n2 columns wide; per column
+ * four doubles take the defined cells of stack 0's rows, then stack 1's, in row order (0.1 for Q0, 0.2 for Q1 and Q2, q otherwise, on
+ * the lowered quality); the base of the greatest ( sum, id ) wins, ties to the highest base, a column nothing was added to gives base 3.
+ * Where no row is left at all the closure is C columns of base 3 (rowless; no offset a.stack.offsets holds leads there).  The rule,
+ * the plan and the file's layout: csrc/dfk_sclosures.h.
+ *   dfk_sclosures_build  works from the context's latest dfk_walks_build*, dfk_scons_build AND dfk_soffsets_build results; the read
+ *                     arguments are the reads they were made from.  DFK_E_STATE without any of them, or when the consensus was not
+ *                     made by dfk_scons_build from these walks or the offsets not by dfk_soffsets_build from this consensus.
+ *   dfk_sclosures_build_arrays  the same stage on host arrays and without a graph: the walks in dfk_walks_fetch's forms, the reads, dims
+ *                     in dfk_scons_fetch's form (4 u32 an element), the offsets in dfk_soffsets_fetch's forms -- so_starts [n_pairs +
+ *                     1], so_words (4 u32 a pair), so_records (24 bytes each) --; closures_per_batch 0 = what fits; with a dir the file
+ *                     is written there.
+ *   DFK_E_ARG for what dfk_scons_build_arrays refuses and for dims that do not say what the walks do, offsets' starts that do not begin
+ *   at 0 or fall, a state other than 0 or 1, offsets of a pair that do not ascend, a kept offset outside [-(n2 - 8), n1 - 8], records
+ *   for a pair that does not yield, words whose kept / closable do not say what the records do.  A refused call changes nothing:
+ *   dfk_sclosures_stats / _fetch / _write serve the latest result of either build, hbm_held is as before.
+ *   dfk_sclosures_stats  out[DFK_SCLOSURES_WORDS]: the counters below
+ *   dfk_sclosures_fetch  pair_first ([n_pairs + 1] words, or NULL), starts ([n_closures + 1] words, or NULL), records (4 u32 a closure,
+ *                     or NULL), the bases a byte each; NULL with cap 0 gives the counts alone; a buffer too small DFK_E_ARG.
+ *   dfk_sclosures_write  into dir (which must exist), whole or not at all.  Little-endian, no byte undefined; a.close.closures' layout:
+ *                       a.stack.closures  "DFKSCLS1" | u64 n closures | u64 n_pairs | (n_pairs + 1) x u64 first closure of each pair |
+ *                                     (n + 1) x u64 starts, in bases | n x 16-byte { u32 pair, i32 offset, u32 cols, u32 rows } | the
+ *                                     bases, a byte each (0..3) | zero bytes to a multiple of 8.
+ *   dfk_allclosures_write  the product of the reference's pair traversal (RunStages.cc:290-325): per pair Stackster's closures, then
+ *                     CloseGap2's, the pairs in order, as dir/a.closures.fastb (a feudal .fastb).  Host only.  DFK_E_STATE unless the
+ *                     context holds a dfk_closures_build and a dfk_sclosures_build result over the same pairs.  out (or NULL):
+ *                     { closures, bases, from Stackster, from CloseGap2 }. */
+#define DFK_SCLOSURES_WORDS 32
+#define DFK_SCLOSURES_PAIRS 0        /* pairs */
+#define DFK_SCLOSURES_YIELDS 1       /* pairs with entries placed on both sides */
+#define DFK_SCLOSURES_CLOSABLE 2     /* pairs with one to three kept offsets: the only ones whose stacks are touched */
+#define DFK_SCLOSURES_NONE 3         /* pairs with no kept offset */
+#define DFK_SCLOSURES_OVER 4         /* pairs with more than three */
+#define DFK_SCLOSURES_CLOSURES 5     /* closures */
+#define DFK_SCLOSURES_COLUMNS 6      /* their columns: the bases */
+#define DFK_SCLOSURES_CELLS 7        /* defined cells added to a column's sums */
+#define DFK_SCLOSURES_LIVE 8         /* live rows walked: per closure those of its pair's two stacks */
+#define DFK_SCLOSURES_ERASED 9       /* rows the two edge trims erased, over all closures */
+#define DFK_SCLOSURES_EMPTY 10       /* columns nothing was added to */
+#define DFK_SCLOSURES_SHORT 11       /* closures shorter than K */
+#define DFK_SCLOSURES_ROWLESS 12     /* closures whose merged stack has no row */
+#define DFK_SCLOSURES_DECODED 13     /* reads gathered, decoded and lowered, a read once a batch */
+#define DFK_SCLOSURES_BATCHES 14     /* batches of closures */
+#define DFK_SCLOSURES_RANGES 15      /* ranges of closable pairs */
+#define DFK_SCLOSURES_VISITS 16      /* ( live row, tile of 256 merged columns ) visits */
+#define DFK_SCLOSURES_SKIPPED 17     /* of them skipped by the whole workgroup: the row's span misses the tile */
+#define DFK_SCLOSURES_US 18          /* microseconds: the build call, */
+#define DFK_SCLOSURES_US_COPY 19     /* the live rows and the gather on the host and the copies, */
+#define DFK_SCLOSURES_US_DECODE 20   /* decode and lowering, */
+#define DFK_SCLOSURES_US_CONS 21     /* the consensus kernel, */
+#define DFK_SCLOSURES_US_ROWS 22     /* the row counts */
+#define DFK_SCLOSURES_SUM 23         /* sum and xor over positions i of h(i, value) (k_digest_seq, salt 0x5C15): the records as u32 words, then the bases */
+#define DFK_SCLOSURES_XOR 24
+int dfk_sclosures_build(dfk_ctx* ctx, const uint8_t* packed_bases, const uint64_t* base_off /* or NULL: dense */, const uint32_t* read_len, const uint8_t* pq, const uint64_t* pq_off, uint64_t n_reads);
+int dfk_sclosures_build_arrays(dfk_ctx* ctx, const uint64_t* starts /* [2 * n_pairs + 1] */, const uint32_t* records /* 8 a walk */, const void* placed, uint64_t n_pairs, const uint8_t* packed_bases,
+                               const uint64_t* base_off, const uint32_t* read_len, const uint8_t* pq, const uint64_t* pq_off, uint64_t n_reads, const uint32_t* dims /* 4 an element */,
+                               const uint64_t* so_starts /* [n_pairs + 1] */, const uint32_t* so_words /* 4 a pair */, const void* so_records, uint64_t closures_per_batch /* 0 = what fits */,
+                               const char* dir /* NULL = no file */);
+int dfk_sclosures_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_SCLOSURES_WORDS] */);
+int dfk_sclosures_fetch(dfk_ctx* ctx, uint64_t* pair_first, uint64_t* starts, uint32_t* records, uint64_t* n_pairs, uint64_t* n_closures, uint8_t* bases, uint64_t bases_cap, uint64_t* n_bases);
+int dfk_sclosures_write(dfk_ctx* ctx, const char* dir);
+int dfk_allclosures_write(dfk_ctx* ctx, const char* dir, uint64_t* out /* [4] or NULL */);
+
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).
  * dfk_paths_digest  fills out[DFK_CHECK_WORDS] with digests that depend on the CONTENT of a.paths, a.paths.inv, a.countsb and

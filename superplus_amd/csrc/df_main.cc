@@ -552,7 +552,7 @@ int main(int argc, char** argv)
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
         {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
-        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}, {"WALKS", "False"}, {"SCONS", "False"}, {"SOFFSETS", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}, {"WALKS", "False"}, {"SCONS", "False"}, {"SOFFSETS", "False"}, {"SCLOSURES", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -614,6 +614,11 @@ int main(int argc, char** argv)
     // with their qualities; it runs where SCONS=True runs
     if (truthy(a["SOFFSETS"]) && !want_scons) give_up("SOFFSETS=True needs SCONS=True: a stack's rows are searched for the 8-mers of the other stack's consensus");
     const bool want_soffsets = truthy(a["SOFFSETS"]);
+
+    // SCLOSURES=True (Stackster's closures per pair, Stackster.cc:712-757, a.<K>/a.stack.closures) works from the walks, their stack consensus' dims, the stack
+    // offsets and the reads with their qualities; it runs where SOFFSETS=True runs.  With CLOSURES=True as well the two closers' closures go into a.<K>/a.closures.fastb
+    if (truthy(a["SCLOSURES"]) && !want_soffsets) give_up("SCLOSURES=True needs SOFFSETS=True: the stacks are merged at the offsets that were kept");
+    const bool want_sclosures = truthy(a["SCLOSURES"]);
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -1159,6 +1164,25 @@ int main(int argc, char** argv)
                                            (unsigned long long)so[DFK_SOFFSETS_DROPPED], (unsigned long long)so[DFK_SOFFSETS_PAIRS_0], (unsigned long long)so[DFK_SOFFSETS_PAIRS_1], (unsigned long long)so[DFK_SOFFSETS_PAIRS_2],
                                            (unsigned long long)so[DFK_SOFFSETS_PAIRS_3], (unsigned long long)so[DFK_SOFFSETS_PAIRS_MORE], (unsigned long long)so[DFK_SOFFSETS_CLOSABLE], (unsigned long long)so[DFK_SOFFSETS_SUM],
                                            (unsigned long long)so[DFK_SOFFSETS_XOR], (unsigned long long)so[DFK_SOFFSETS_BATCHES], (unsigned long long)so[DFK_SOFFSETS_RANGES]);
+                                    if (want_sclosures) {                       // Stackster's closures per pair (Stackster.cc:712-757): a.<K>/a.stack.closures, after a.stack.offsets
+                                        uint64_t sl[DFK_SCLOSURES_WORDS] = {};
+                                        const int lrc = fast ? dfk_sclosures_build(ctx, h_packed + (n_reads ? ld64(h_boff) : 0), nullptr, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, n_reads)      // (dense: validated at load)
+                                                             : dfk_sclosures_build(ctx, h_packed, (const uint64_t*)h_boff, (const uint32_t*)h_len, h_pq, (const uint64_t*)h_qoff, n_reads);
+                                        if (lrc || dfk_sclosures_write(ctx, dir.c_str()) || dfk_sclosures_stats(ctx, sl)) throw std::runtime_error(dfk_last_error());
+                                        printf("DF_SCLOSURES {\"pairs\": %llu, \"yields\": %llu, \"closable\": %llu, \"none\": %llu, \"over\": %llu, \"closures\": %llu, \"columns\": %llu, "
+                                               "\"a.stack.closures\": \"%016llx%016llx\", \"cells\": %llu, \"live_rows\": %llu, \"erased\": %llu, \"empty\": %llu, \"short\": %llu, \"rowless\": %llu, \"batches\": %llu, "
+                                               "\"ranges\": %llu}\n",
+                                               (unsigned long long)sl[DFK_SCLOSURES_PAIRS], (unsigned long long)sl[DFK_SCLOSURES_YIELDS], (unsigned long long)sl[DFK_SCLOSURES_CLOSABLE], (unsigned long long)sl[DFK_SCLOSURES_NONE],
+                                               (unsigned long long)sl[DFK_SCLOSURES_OVER], (unsigned long long)sl[DFK_SCLOSURES_CLOSURES], (unsigned long long)sl[DFK_SCLOSURES_COLUMNS], (unsigned long long)sl[DFK_SCLOSURES_SUM],
+                                               (unsigned long long)sl[DFK_SCLOSURES_XOR], (unsigned long long)sl[DFK_SCLOSURES_CELLS], (unsigned long long)sl[DFK_SCLOSURES_LIVE], (unsigned long long)sl[DFK_SCLOSURES_ERASED],
+                                               (unsigned long long)sl[DFK_SCLOSURES_EMPTY], (unsigned long long)sl[DFK_SCLOSURES_SHORT], (unsigned long long)sl[DFK_SCLOSURES_ROWLESS], (unsigned long long)sl[DFK_SCLOSURES_BATCHES],
+                                               (unsigned long long)sl[DFK_SCLOSURES_RANGES]);
+                                        if (want_closures) {                    // both closers' closures, a pair at a time (RunStages.cc:290-325): a.<K>/a.closures.fastb
+                                            uint64_t all[4] = {};
+                                            if (dfk_allclosures_write(ctx, dir.c_str(), all)) throw std::runtime_error(dfk_last_error());
+                                            printf("found %llu closures\n", (unsigned long long)all[0]);
+                                        }
+                                    }
                                 }
                             }
                         }

@@ -18,6 +18,7 @@ struct ClosuresResult {
     std::vector<uint8_t> bases;                   // padded with zero bytes to a multiple of 8
     uint64_t n_bases = 0;
     uint64_t stats[DFK_CLOSURES_WORDS] = {};
+    std::vector<int32_t> pairs;                   // dfk_closures_build: the pairs it was made for (dfk_allclosures_write asks)
 };
 void closures_result_free(ClosuresResult* r) { delete r; }
 
@@ -259,6 +260,7 @@ int dfk_closures_build(dfk_ctx* c, const uint8_t* packed, const uint64_t* base_o
     const int32_t none[2] = {0, 0};
     std::unique_ptr<ClosuresResult> R(new ClosuresResult);
     if (int rc = closures_build(c, X.S, n_pairs ? K->pairs.data() : none, n_pairs, off_first.data(), offsets.data(), 0, R.get())) return rc;     // (refused: the earlier result is still served)
+    R->pairs = K->pairs;
     closures_keep(c, R.release());
     return 0;
     });

@@ -57,6 +57,8 @@ struct HostGraph {
     void (*scons_free)(struct SconsResult*) = nullptr;
     struct SoffsetsResult* soffsets = nullptr;                       // the latest dfk_soffsets_build*'s result (dfk_soffsets.inc)
     void (*soffsets_free)(struct SoffsetsResult*) = nullptr;
+    struct SclosuresResult* sclosures = nullptr;                     // the latest dfk_sclosures_build*'s result (dfk_sclosures.inc)
+    void (*sclosures_free)(struct SclosuresResult*) = nullptr;
     ~HostGraph()
     {
         if (paths && paths_free) paths_free(paths);
@@ -70,6 +72,7 @@ struct HostGraph {
         if (walks && walks_free) walks_free(walks);
         if (scons && scons_free) scons_free(scons);
         if (soffsets && soffsets_free) soffsets_free(soffsets);
+        if (sclosures && sclosures_free) sclosures_free(sclosures);
     }
 };
 

@@ -18,6 +18,7 @@ struct SconsResult {
     std::vector<uint16_t> counts;
     uint64_t stats[DFK_SCONS_WORDS] = {};
     uint64_t walks_serial = 0;                    // dfk_scons_build: the walks it was made from (0: from arrays); dfk_soffsets_build asks
+    uint64_t serial = 0;                          // dfk_scons_build: which build made it; dfk_soffsets_build notes it, dfk_sclosures_build asks for the same
 };
 void scons_result_free(SconsResult* r) { delete r; }
 
@@ -281,7 +282,7 @@ int dfk_scons_build(dfk_ctx* c, const uint8_t* packed, const uint64_t* base_off,
     const SconsSource S{W->recs.size() / 2, W->starts.data(), W->recs.empty() ? &no_rec : W->recs.data(), W->locs.empty() ? &no_loc : W->locs.data(), &reads, pq, pq_off};
     std::unique_ptr<SconsResult> R(new SconsResult);
     if (int rc = scons_build(c, S, 0, R.get())) return rc;                                  // (refused: the earlier result is still served)
-    R->walks_serial = W->serial;
+    R->walks_serial = W->serial; R->serial = cons_next_serial();
     scons_keep(c, R.release());
     return 0;
     });

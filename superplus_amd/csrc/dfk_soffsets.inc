@@ -16,6 +16,7 @@ struct SoffsetsResult {
     std::vector<dfk_soffsets::PairWords> words;   // [n_pairs]
     std::vector<dfk_soffsets::Rec> recs;
     uint64_t stats[DFK_SOFFSETS_WORDS] = {};
+    uint64_t scons_serial = 0;                    // dfk_soffsets_build: the stack consensus it was made from (0: from arrays); dfk_sclosures_build asks
 };
 void soffsets_result_free(SoffsetsResult* r) { delete r; }
 
@@ -304,6 +305,7 @@ int dfk_soffsets_build(dfk_ctx* c, const uint8_t* packed, const uint64_t* base_o
     if (K->dims.size() != W->recs.size()) return fail(DFK_E_STATE, "the stack consensus holds %llu elements, the walks %llu", (unsigned long long)K->dims.size(), (unsigned long long)W->recs.size());
     std::unique_ptr<SoffsetsResult> R(new SoffsetsResult);
     if (int rc = soffsets_build(c, X, 0, R.get())) return rc;                               // (refused: the earlier result is still served)
+    R->scons_serial = K->serial;
     soffsets_keep(c, R.release());
     return 0;
     });

@@ -19,6 +19,7 @@ struct WalksResult {
     uint64_t n_reads = 0;                         // the reads it was made from: dfk_scons_build asks for as many
     uint64_t stats[DFK_WALKS_WORDS] = {};
     uint64_t serial = 0;                          // which build made it: dfk_scons_build notes it, dfk_soffsets_build asks for the same
+    std::vector<int32_t> pairs;                   // dfk_walks_build: the pairs it was made for (dfk_allclosures_write asks)
 };
 void walks_result_free(WalksResult* r) { delete r; }
 
@@ -433,6 +434,7 @@ int dfk_walks_build(dfk_ctx* c, const int32_t* pairs, uint64_t n_pairs, const ui
     const WalksSource S{inv.size(), inv.data(), n_ce, C->ce.data(), store.data(), store.size(), edge_at.data(), edge_len.data(), C->read_first.data(), C->reads.data(), &reads, pq, pq_off};
     std::unique_ptr<WalksResult> R(new WalksResult);
     if (int rc = walks_build(c, S, n_pairs ? pairs : none, n_pairs, 0, R.get())) return rc;          // (refused: the earlier result is still served)
+    R->pairs.assign(pairs, pairs + 2 * n_pairs);
     walks_keep(c, R.release());
     return 0;
     });

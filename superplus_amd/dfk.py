@@ -41,6 +41,7 @@ EXPORTS = [
     "dfk_walks_build", "dfk_walks_build_arrays", "dfk_walks_stats", "dfk_walks_fetch", "dfk_walks_write",
     "dfk_scons_build", "dfk_scons_build_arrays", "dfk_scons_stats", "dfk_scons_fetch", "dfk_scons_write",
     "dfk_soffsets_build", "dfk_soffsets_build_arrays", "dfk_soffsets_stats", "dfk_soffsets_fetch", "dfk_soffsets_write",
+    "dfk_sclosures_build", "dfk_sclosures_build_arrays", "dfk_sclosures_stats", "dfk_sclosures_fetch", "dfk_sclosures_write", "dfk_allclosures_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -98,6 +99,12 @@ SOFFSETS = ["pairs", "yields", "rows", "kmers", "acceptable", "hits", "seen", "d
             "pairs_more", "closable", "live", "decoded", "batches", "ranges", "us", "us_copy", "us_decode", "us_search", "us_emit", "sum", "xor"]
 SOFFSETS_FILE = "a.stack.offsets"
 SOFFSETS_RECORD = np.dtype([("offset", "<i4"), ("results", "<u4"), ("best_bits", "<f8"), ("state", "<u4"), ("zero", "<u4")])
+# dfk_sclosures_stats' words (include/dfk.h, DFK_SCLOSURES_*)
+SCLOSURES_WORDS = 32
+SCLOSURES = ["pairs", "yields", "closable", "none", "over", "closures", "columns", "cells", "live", "erased", "empty", "short", "rowless", "decoded", "batches", "ranges", "visits", "skipped",
+             "us", "us_copy", "us_decode", "us_cons", "us_rows", "sum", "xor"]
+SCLOSURES_FILE = "a.stack.closures"
+ALLCLOSURES_FILE = "a.closures.fastb"
 # dfk_adj_outcome's codes (include/dfk.h, DFK_ADJ_*)
 ADJ_OUTCOMES = ["not applicable", "used", "discarded: guess too low", "discarded: list problem", "no block", "dropped for an allocation",
                 "switched off"]
@@ -817,6 +824,61 @@ class Dfk:
     def soffsets_write(self, directory):
         """dfk_soffsets_write: a.stack.offsets into `directory` (which must exist)."""
         _check(lib().dfk_soffsets_write(self._ctx, None if directory is None else str(directory).encode()))
+
+    def sclosures_build(self, packed, base_off, read_len, pq_bytes, pq_off):
+        """dfk_sclosures_build: Stackster's closures per pair, after walks_build, scons_build and soffsets_build; the reads are the ones
+        they were made from with their PQVec qualities.  Returns sclosures_stats()."""
+        n = 0 if read_len is None else len(read_len)
+        packed, read_len, pq_bytes = (None if x is None else np.ascontiguousarray(x, t) for x, t in ((packed, np.uint8), (read_len, np.uint32), (pq_bytes, np.uint8)))
+        base_off, pq_off = (None if x is None else np.ascontiguousarray(x, np.uint64) for x in (base_off, pq_off))
+        _check(lib().dfk_sclosures_build(self._ctx, _p(packed), _p(base_off), _p(read_len), _p(pq_bytes), _p(pq_off), C.c_uint64(n)))
+        return self.sclosures_stats()
+
+    def sclosures_build_arrays(self, a, closures_per_batch=0, directory=None, **change):
+        """dfk_sclosures_build_arrays: the same stage on arrays.  a: scons_build_arrays' dict and dims uint32[2 p, 4] (scons_fetch's form),
+        so_starts uint64[p + 1], so_words uint32[p, 4], so_records SOFFSETS_RECORD[] (soffsets_fetch's forms); a key in `change` replaces
+        one (None: a NULL pointer).  With a directory a.stack.closures is written there.  Returns sclosures_stats()."""
+        a = dict(a); a.update(change)
+        kinds = dict(starts=np.uint64, records=np.uint32, placed=WALKS_PLACED, read_packed=np.uint8, read_off=np.uint64, read_len=np.uint32, pq=np.uint8, pq_off=np.uint64,
+                     dims=np.uint32, so_starts=np.uint64, so_words=np.uint32, so_records=SOFFSETS_RECORD)
+        n = {k: (0 if a[k] is None else len(a[k])) for k in kinds}
+        # (an empty array still has an address: NULL is for what is left out on purpose)
+        v = {k: None if a[k] is None else np.ascontiguousarray(a[k] if len(a[k]) else np.zeros(1, t), t) for k, t in kinds.items()}
+        _check(lib().dfk_sclosures_build_arrays(self._ctx, _p(v["starts"]), _p(v["records"]), _p(v["placed"]), C.c_uint64((n["starts"] - 1) // 2 if n["starts"] else n["records"] // 2), _p(v["read_packed"]), _p(v["read_off"]),
+                                                _p(v["read_len"]), _p(v["pq"]), _p(v["pq_off"]), C.c_uint64(n["read_len"]), _p(v["dims"]), _p(v["so_starts"]), _p(v["so_words"]), _p(v["so_records"]),
+                                                C.c_uint64(closures_per_batch), None if directory is None else str(directory).encode()))
+        return self.sclosures_stats()
+
+    def sclosures_stats(self):
+        """dfk_sclosures_stats: {counter: value} -- pairs, yielding pairs, closable pairs, pairs with no kept offset and with more than
+        three, closures, columns, cells added, live rows walked, rows erased by the edge trims, empty columns, closures shorter than K,
+        rowless closures, decoded reads, batches, ranges, tile visits and those skipped, times, digest."""
+        out = (C.c_uint64 * SCLOSURES_WORDS)()
+        _check(lib().dfk_sclosures_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(SCLOSURES)}
+
+    def sclosures_fetch(self):
+        """dfk_sclosures_fetch: dict(pair_first uint64[p + 1], starts uint64[n + 1], records int64[n, 4] (pair, offset, cols, rows), bases
+        uint8[columns])."""
+        npairs, nc, nb = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().dfk_sclosures_fetch(self._ctx, None, None, None, C.byref(npairs), C.byref(nc), None, C.c_uint64(0), C.byref(nb)))
+        pair_first, starts = np.zeros(npairs.value + 1, np.uint64), np.zeros(nc.value + 1, np.uint64)
+        recs, bases = np.zeros((max(1, nc.value), 4), np.uint32), np.zeros(max(1, nb.value), np.uint8)
+        _check(lib().dfk_sclosures_fetch(self._ctx, _p(pair_first), _p(starts), _p(recs), C.byref(npairs), C.byref(nc), _p(bases), C.c_uint64(nb.value), C.byref(nb)))
+        recs = recs[: nc.value].astype(np.int64)
+        recs[:, 1] = recs[:, 1].astype(np.uint32).view(np.int32) if len(recs) else recs[:, 1]
+        return dict(pair_first=pair_first, starts=starts, records=recs, bases=bases[: nb.value])
+
+    def sclosures_write(self, directory):
+        """dfk_sclosures_write: a.stack.closures into `directory` (which must exist)."""
+        _check(lib().dfk_sclosures_write(self._ctx, None if directory is None else str(directory).encode()))
+
+    def allclosures_write(self, directory):
+        """dfk_allclosures_write: a.closures.fastb into `directory` -- per pair Stackster's closures, then CloseGap2's, after closures_build
+        and sclosures_build over the same pairs.  Returns dict(closures, bases, stackster, closegap2)."""
+        out = (C.c_uint64 * 4)()
+        _check(lib().dfk_allclosures_write(self._ctx, None if directory is None else str(directory).encode(), out))
+        return dict(closures=int(out[0]), bases=int(out[1]), stackster=int(out[2]), closegap2=int(out[3]))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
