@@ -969,6 +969,71 @@ int dfk_sclosures_fetch(dfk_ctx* ctx, uint64_t* pair_first, uint64_t* starts, ui
 int dfk_sclosures_write(dfk_ctx* ctx, const char* dir);
 int dfk_allclosures_write(dfk_ctx* ctx, const char* dir, uint64_t* out /* [4] or NULL */);
 
+/* ---- the patched graph: the closures go into the assembly (10X/runstages/RunStages.cc:330-360) ----
+ * Replaces BuildAll (paths/long/large/GapToyTools4.cc:132-159), buildBigKHBVFromReads( K, allx, 4, &hb3, &allx_paths )
+ * (kmers/BigKPather.cc:450-535) and the lines that keep the old edges' paths as to3 / left3 (RunStages.cc:355-358): what TranslatePaths
+ * will move the read paths onto the new graph with.  The rule, the shared pieces, the order of work and a.patch.to3's layout:
+ * csrc/dfk_patch.h.
+ *   dfk_patch_build   works from the context's graph and the closures of BOTH closers: DFK_E_STATE unless the context holds a built
+ *                     graph, a dfk_closures_build and a dfk_sclosures_build result made for the same pairs (dfk_allclosures_write's
+ *                     test); the closures are taken in the combined list's order.  kmers_per_batch: closure K-mer positions looked up
+ *                     at a time, 0 = what fits.
+ *   dfk_patch_build_arrays  the same stage on host arrays and without a graph in the context (its K is the context's): the graph as
+ *                     inv, to_left, to_right [n_edges], its edges' bases packed as a .fastb packs them, edge e at byte edge_off[e] with
+ *                     edge_len[e] bases; the closures as starts [n_closures + 1] into closure_bases (a base a byte, 0-3).  A table that
+ *                     does not hold together is DFK_E_ARG: inv no involution or inv[e] not e's reverse complement, an end that is no
+ *                     vertex, an edge shorter than K, edges at a vertex that do not share its K-1 bases, a K-mer on two canonical edges; closure starts
+ *                     that do not begin at 0 or fall, a closure base above 3.
+ *   After any refusal the earlier result is still served.  Every device block comes from the arena and is back on return (hbm_held is
+ *   as before); the context's graph, index, filter and pathing state are not touched.
+ *   dfk_patch_stats   out[DFK_PATCH_WORDS]: the counters below
+ *   dfk_patch_fetch   the sizes (any may be NULL), to3_first ([n_edges + 1]), to3 ([n_to3]), left3 ([n_edges]) and hb3's kmers, inv,
+ *                     to_left, to_right ([n_edges3] each); an array that is NULL is left out
+ *   dfk_patch_write   into dir (which must exist): hb3's eight graph files as a.patch.{k,hbv,hbx,to_left,to_right,inv,fastb,kmers}, by
+ *                     the code that writes a.*, and a.patch.to3 ("DFKPTO31", csrc/dfk_patch.h) */
+#define DFK_PATCH_WORDS 40
+#define DFK_PATCH_EDGES 0           /* old edges, */
+#define DFK_PATCH_CANONICAL 1       /* of them e <= inv[e], */
+#define DFK_PATCH_VERTICES 2        /* vertices, */
+#define DFK_PATCH_CROSSINGS 3       /* vertex crossings: the (K+1)-mers BuildAll adds */
+#define DFK_PATCH_CLOSURES 4        /* closures, */
+#define DFK_PATCH_SHORT 5           /* of them shorter than K, */
+#define DFK_PATCH_POSITIONS 6       /* their K-mer positions */
+#define DFK_PATCH_FOUND 7           /* closure K-mers found on the old edges, */
+#define DFK_PATCH_NEW 8             /* not found, */
+#define DFK_PATCH_NEW_UNIQUE 9      /* and those after de-duplication: the dictionary's second part */
+#define DFK_PATCH_BITS_ADDED 10     /* context bits the closures added to old entries */
+#define DFK_PATCH_KMERS3 11         /* hb3: K-mers, */
+#define DFK_PATCH_CANONICAL3 12     /* canonical edges, */
+#define DFK_PATCH_VERTICES3 13      /* vertices, */
+#define DFK_PATCH_EDGES3 14         /* edges, */
+#define DFK_PATCH_SINGLE3 15        /* canonical edges of one K-mer, */
+#define DFK_PATCH_CYCLE_KMERS 16    /* K-mers on branch-free cycles */
+#define DFK_PATCH_PATH1 17          /* old edges whose path has 1, */
+#define DFK_PATCH_PATH2 18          /* 2, */
+#define DFK_PATCH_PATH3 19          /* 3 or more ids */
+#define DFK_PATCH_TO3 20            /* to3 entries */
+#define DFK_PATCH_LEFT3 21          /* old edges with left3 != 0 */
+#define DFK_PATCH_BATCHES 22        /* batches of closure K-mer positions */
+#define DFK_PATCH_US 23             /* microseconds: the build call from its first statement, */
+#define DFK_PATCH_US_ENTRIES 24     /* the entries kernel, */
+#define DFK_PATCH_US_INDEX 25       /* the index over them and the check, */
+#define DFK_PATCH_US_CLOSURES 26    /* the closure K-mers, */
+#define DFK_PATCH_US_SORT 27        /* the novel K-mers sorted and merged (host), */
+#define DFK_PATCH_US_GRAPH 28       /* the graph kernels, */
+#define DFK_PATCH_US_NUMBER 29      /* build_hbv (host), */
+#define DFK_PATCH_US_PATHS 30       /* heads, scan and emit, */
+#define DFK_PATCH_US_COPY 31        /* the tables unpacked and checked, packing, copies and the paths' layout on the host */
+#define DFK_PATCH_SUM 32            /* sum and xor over positions i of h(i, value) (k_digest_seq's h, salt 0x9A7C): to3_first, then to3, then left3 */
+#define DFK_PATCH_XOR 33
+int dfk_patch_build(dfk_ctx* ctx, uint64_t kmers_per_batch);
+int dfk_patch_build_arrays(dfk_ctx* ctx, uint64_t n_edges, uint64_t n_vertices, const int32_t* inv, const int32_t* to_left, const int32_t* to_right, const uint8_t* packed_bases,
+                           const uint64_t* edge_off, const uint32_t* edge_len, uint64_t n_closures, const uint64_t* closure_starts, const uint8_t* closure_bases, uint64_t kmers_per_batch);
+int dfk_patch_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_PATCH_WORDS] */);
+int dfk_patch_fetch(dfk_ctx* ctx, uint64_t* n_edges, uint64_t* n_to3, uint64_t* n_edges3, uint64_t* to3_first, int32_t* to3, int32_t* left3, int32_t* kmers3, int32_t* inv3, int32_t* to_left3,
+                    int32_t* to_right3);
+int dfk_patch_write(dfk_ctx* ctx, const char* dir);
+
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).
  * dfk_paths_digest  fills out[DFK_CHECK_WORDS] with digests that depend on the CONTENT of a.paths, a.paths.inv, a.countsb and

@@ -552,7 +552,7 @@ int main(int argc, char** argv)
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
         {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
-        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}, {"WALKS", "False"}, {"SCONS", "False"}, {"SOFFSETS", "False"}, {"SCLOSURES", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}, {"WALKS", "False"}, {"SCONS", "False"}, {"SOFFSETS", "False"}, {"SCLOSURES", "False"}, {"PATCH", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -619,6 +619,11 @@ int main(int argc, char** argv)
     // offsets and the reads with their qualities; it runs where SOFFSETS=True runs.  With CLOSURES=True as well the two closers' closures go into a.<K>/a.closures.fastb
     if (truthy(a["SCLOSURES"]) && !want_soffsets) give_up("SCLOSURES=True needs SOFFSETS=True: the stacks are merged at the offsets that were kept");
     const bool want_sclosures = truthy(a["SCLOSURES"]);
+
+    // PATCH=True (the closures go into the assembly, RunStages.cc:330-360: BuildAll, buildBigKHBVFromReads, to3 / left3; a.<K>/a.patch.*) works from the graph and
+    // the combined list of both closers' closures; it runs where a.closures.fastb is written and, like HOPS=True, which the closers need, on one GPU only
+    if (truthy(a["PATCH"]) && !(want_closures && want_sclosures)) give_up("PATCH=True needs CLOSURES=True and SCLOSURES=True: the patched graph is built from both closers' closures");
+    const bool want_patch = truthy(a["PATCH"]);
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -1181,6 +1186,16 @@ int main(int argc, char** argv)
                                             uint64_t all[4] = {};
                                             if (dfk_allclosures_write(ctx, dir.c_str(), all)) throw std::runtime_error(dfk_last_error());
                                             printf("found %llu closures\n", (unsigned long long)all[0]);
+                                            if (want_patch) {                   // the closures into the assembly (RunStages.cc:330-360): a.<K>/a.patch.*, after a.closures.fastb
+                                                uint64_t pt[DFK_PATCH_WORDS] = {};
+                                                if (dfk_patch_build(ctx, 0) || dfk_patch_write(ctx, dir.c_str()) || dfk_patch_stats(ctx, pt)) throw std::runtime_error(dfk_last_error());
+                                                printf("DF_PATCH {\"edges\": %llu, \"closures\": %llu, \"positions\": %llu, \"found\": %llu, \"new\": %llu, \"new_unique\": %llu, \"bits_added\": %llu, "
+                                                       "\"kmers3\": %llu, \"canonical3\": %llu, \"vertices3\": %llu, \"edges3\": %llu, \"to3\": %llu, \"left3\": %llu, \"a.patch.to3\": \"%016llx%016llx\", \"batches\": %llu}\n",
+                                                       (unsigned long long)pt[DFK_PATCH_EDGES], (unsigned long long)pt[DFK_PATCH_CLOSURES], (unsigned long long)pt[DFK_PATCH_POSITIONS], (unsigned long long)pt[DFK_PATCH_FOUND],
+                                                       (unsigned long long)pt[DFK_PATCH_NEW], (unsigned long long)pt[DFK_PATCH_NEW_UNIQUE], (unsigned long long)pt[DFK_PATCH_BITS_ADDED], (unsigned long long)pt[DFK_PATCH_KMERS3],
+                                                       (unsigned long long)pt[DFK_PATCH_CANONICAL3], (unsigned long long)pt[DFK_PATCH_VERTICES3], (unsigned long long)pt[DFK_PATCH_EDGES3], (unsigned long long)pt[DFK_PATCH_TO3],
+                                                       (unsigned long long)pt[DFK_PATCH_LEFT3], (unsigned long long)pt[DFK_PATCH_SUM], (unsigned long long)pt[DFK_PATCH_XOR], (unsigned long long)pt[DFK_PATCH_BATCHES]);
+                                            }
                                         }
                                     }
                                 }

@@ -59,6 +59,8 @@ struct HostGraph {
     void (*soffsets_free)(struct SoffsetsResult*) = nullptr;
     struct SclosuresResult* sclosures = nullptr;                     // the latest dfk_sclosures_build*'s result (dfk_sclosures.inc)
     void (*sclosures_free)(struct SclosuresResult*) = nullptr;
+    struct PatchResult* patch = nullptr;                             // the latest dfk_patch_build*'s result (dfk_patch.inc)
+    void (*patch_free)(struct PatchResult*) = nullptr;
     ~HostGraph()
     {
         if (paths && paths_free) paths_free(paths);
@@ -73,6 +75,7 @@ struct HostGraph {
         if (scons && scons_free) scons_free(scons);
         if (soffsets && soffsets_free) soffsets_free(soffsets);
         if (sclosures && sclosures_free) sclosures_free(sclosures);
+        if (patch && patch_free) patch_free(patch);
     }
 };
 
@@ -296,7 +299,8 @@ void packed_edge(const HostGraph& G, const HostGraph::HEdge& e, std::vector<uint
     }
 }
 
-void write_graph_files(const HostGraph& G, const std::string& dir)
+// (stem: "a." for the graph's files, "a.patch." for the patched graph's, dfk_patch.inc)
+void write_graph_files(const HostGraph& G, const std::string& dir, const std::string& stem = "a.")
 {
     const uint32_t K = G.K;
     const size_t E = G.he.size();
@@ -308,27 +312,27 @@ void write_graph_files(const HostGraph& G, const std::string& dir)
         // reverse complement": the same canonical edge in the other orientation
         inv[e] = G.he[e].rc ? G.fwd[G.he[e].ce] : G.rev[G.he[e].ce];
     }
-    { OutFile f(dir + "/a.k"); const std::string s = std::to_string(K) + "\n"; f.raw(s.data(), s.size()); f.close(); }
+    { OutFile f(dir + "/" + stem + "k"); const std::string s = std::to_string(K) + "\n"; f.raw(s.data(), s.size()); f.close(); }
     std::vector<uint8_t> pk;
     auto edges_vec = [&](OutFile& f) {                                   // vec<basevector>: u64 n, per edge u32 length + packed bases (FieldVec::writeBinary)
         f.pod<uint64_t>(E);
         for (size_t e = 0; e < E; ++e) { packed_edge(G, G.he[e], &pk); f.pod<uint32_t>(G.ce[G.he[e].ce].n + K - 1); f.raw(pk.data(), pk.size()); }
     };
-    { OutFile f(dir + "/a.hbv"); f.raw("BINWRITE", 8); f.pod<int32_t>((int32_t)K);            // K | digraphE: from, from_edge_obj, to_edge_obj, edges
+    { OutFile f(dir + "/" + stem + "hbv"); f.raw("BINWRITE", 8); f.pod<int32_t>((int32_t)K);            // K | digraphE: from, from_edge_obj, to_edge_obj, edges
       f.vecvec_i32(G.from_start, G.from_v); f.vecvec_i32(G.from_start, G.from_e); f.vecvec_i32(G.to_start, G.to_e); edges_vec(f); f.close(); }
-    { OutFile f(dir + "/a.to_left"); f.raw("BINWRITE", 8); f.vec_i32(to_left); f.close(); }
-    { OutFile f(dir + "/a.to_right"); f.raw("BINWRITE", 8); f.vec_i32(to_right); f.close(); }
-    { OutFile f(dir + "/a.inv"); f.raw("BINWRITE", 8); f.vec_i32(inv); f.close(); }
-    { OutFile f(dir + "/a.hbx"); f.raw("BINWRITE", 8); f.pod<int32_t>((int32_t)K);            // K | digraphEX (DigraphTemplate.h:2593-2599)
+    { OutFile f(dir + "/" + stem + "to_left"); f.raw("BINWRITE", 8); f.vec_i32(to_left); f.close(); }
+    { OutFile f(dir + "/" + stem + "to_right"); f.raw("BINWRITE", 8); f.vec_i32(to_right); f.close(); }
+    { OutFile f(dir + "/" + stem + "inv"); f.raw("BINWRITE", 8); f.vec_i32(inv); f.close(); }
+    { OutFile f(dir + "/" + stem + "hbx"); f.raw("BINWRITE", 8); f.pod<int32_t>((int32_t)K);            // K | digraphEX (DigraphTemplate.h:2593-2599)
       f.serf_i32(G.from_start, G.from_v); f.serf_i32(G.to_start, G.to_v); f.serf_i32(G.from_start, G.from_e); f.serf_i32(G.to_start, G.to_e); edges_vec(f);
       f.vec_i32(to_left); f.vec_i32(to_right); f.close(); }
-    { OutFile f(dir + "/a.kmers"); f.raw("BINWRITE", 8); f.vec_i32(kmers); f.close(); }
+    { OutFile f(dir + "/" + stem + "kmers"); f.raw("BINWRITE", 8); f.vec_i32(kmers); f.close(); }
     {   // a.fastb: feudal file, var = packed bases, fixed = u32 lengths (feudal/FeudalFileWriter.cc:26-121)
         uint64_t var = 0;
         std::vector<uint64_t> off(E + 1);
         for (size_t e = 0; e < E; ++e) { off[e] = 24 + var; var += (G.ce[G.he[e].ce].n + K - 1 + 3) / 4; }
         off[E] = 24 + var;
-        OutFile f(dir + "/a.fastb");
+        OutFile f(dir + "/" + stem + "fastb");
         struct { uint32_t n; uint8_t flags, szFixed, szX, szA; uint64_t varTab, fixedOff; } h{(uint32_t)E, 1, 4, 16, 1, 24 + var, 24 + var + 8 * (E + 1)};
         static_assert(sizeof h == 24, "feudal control block");
         f.raw(&h, 24);
@@ -341,21 +345,12 @@ void write_graph_files(const HostGraph& G, const std::string& dir)
 
 HostGraph* graph_of(dfk_ctx* c);
 
+// The device half: the canonical edges of the `n` entries a part table names (n > 0), into G->ce and G->bases; the k-mer index, the
+// edges' records and their bases stay on the device in G->d_index, G->d_recs and G->d_store, and every entry holds its (edge, offset).
+// graph_build_typed runs it over the context's dictionary, dfk_patch.inc over a dictionary and a HostGraph of its own.
 template <int K>
-int graph_build_typed(dfk_ctx* c, HostGraph* G)
+int graph_edges_typed(dfk_ctx* c, const PartTable& pt, const uint64_t n, HostGraph* G, float* ms_out)
 {
-    const uint64_t n = c->n_solid;
-    G->K = K; G->ce.clear(); G->bases.clear(); G->built = false;
-    if (G->paths) { G->paths_free(G->paths); G->paths = nullptr; }
-    c->release(G->d_index); c->release(G->d_recs); c->release(G->d_store); c->release(G->d_filter); G->filter_words = 0;
-    if (n >= 0xFFFFFFFFull) return fail(DFK_E_ARG, "the edge builder indexes k-mers with 32 bits: %llu solid k-mers", (unsigned long long)n);
-    if (c->parts.size() > (size_t)GRAPH_MAX_PARTS) return fail(DFK_E_ARG, "more than %d dictionary parts", GRAPH_MAX_PARTS);
-    if (!n) { build_hbv(*G); return 0; }
-    PartTable pt{};
-    pt.n_parts = 0;
-    uint64_t at = 0;
-    for (const dfk_ctx::Part& p : c->parts) { if (!p.n) continue; pt.start[pt.n_parts] = at; pt.ptr[pt.n_parts] = (uint4*)p.buf.p; ++pt.n_parts; at += p.n; }
-    pt.start[pt.n_parts] = at;
     Timer t(c->stream);
     t.start();
     const uint64_t slots = std::max<uint64_t>(1024, (2 * n + 2 + 1) & ~1ull);          // load 1/2 (even: filled eight bytes at a time)
@@ -470,8 +465,28 @@ int graph_build_typed(dfk_ctx* c, HostGraph* G)
     TRACE("graph: the longest edge has %u k-mers", longest);
     c->release(ctr); c->release(d_bad);
     G->d_index = index; G->index_slots = slots; G->d_recs = recs; G->d_store = store;     // kept: read pathing looks k-mers up and compares bases
-    const float ms_edges = t.stop();
+    *ms_out = t.stop();
     if (kmers_on_edges != n) return fail(DFK_E_HIP, "graph: the edges hold %llu k-mers, the dictionary %llu", (unsigned long long)kmers_on_edges, (unsigned long long)n);
+    return 0;
+}
+
+template <int K>
+int graph_build_typed(dfk_ctx* c, HostGraph* G)
+{
+    const uint64_t n = c->n_solid;
+    G->K = K; G->ce.clear(); G->bases.clear(); G->built = false;
+    if (G->paths) { G->paths_free(G->paths); G->paths = nullptr; }
+    c->release(G->d_index); c->release(G->d_recs); c->release(G->d_store); c->release(G->d_filter); G->filter_words = 0;
+    if (n >= 0xFFFFFFFFull) return fail(DFK_E_ARG, "the edge builder indexes k-mers with 32 bits: %llu solid k-mers", (unsigned long long)n);
+    if (c->parts.size() > (size_t)GRAPH_MAX_PARTS) return fail(DFK_E_ARG, "more than %d dictionary parts", GRAPH_MAX_PARTS);
+    if (!n) { build_hbv(*G); return 0; }
+    PartTable pt{};
+    pt.n_parts = 0;
+    uint64_t at = 0;
+    for (const dfk_ctx::Part& p : c->parts) { if (!p.n) continue; pt.start[pt.n_parts] = at; pt.ptr[pt.n_parts] = (uint4*)p.buf.p; ++pt.n_parts; at += p.n; }
+    pt.start[pt.n_parts] = at;
+    float ms_edges = 0;
+    if (int rc = graph_edges_typed<K>(c, pt, n, G, &ms_edges)) return rc;
     // The filter the pather puts in front of the index (two bytes a k-mer, 0.1-0.2 s of scattered atomicOr at configs[1]) needs
     // the dictionary's keys and nothing of the graph: it is made NOW, on the device, while the host numbers vertices and edges
     // -- when the reads the count kept say how much room the pathing will want (otherwise dfk_paths_build makes it).
@@ -491,7 +506,7 @@ int graph_build_typed(dfk_ctx* c, HostGraph* G)
     const float ms_hbv = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c->st.reserved[1] = (uint64_t)(ms_edges * 1000.0f);                       // microseconds: edges on the device, numbering on the host
     c->st.reserved[2] = (uint64_t)(ms_hbv * 1000.0f);
-    TRACE("graph: %llu canonical edges in %.1f ms, %llu vertices and %zu edges numbered in %.1f ms", (unsigned long long)n_edges, ms_edges,
+    TRACE("graph: %llu canonical edges in %.1f ms, %llu vertices and %zu edges numbered in %.1f ms", (unsigned long long)G->ce.size(), ms_edges,
           (unsigned long long)G->n_vertices, G->he.size(), ms_hbv);
     c->sorted_ok = c->sorted_pre_ok = false;                                   // the entries now carry (edge, offset)
     return 0;

@@ -42,6 +42,7 @@ EXPORTS = [
     "dfk_scons_build", "dfk_scons_build_arrays", "dfk_scons_stats", "dfk_scons_fetch", "dfk_scons_write",
     "dfk_soffsets_build", "dfk_soffsets_build_arrays", "dfk_soffsets_stats", "dfk_soffsets_fetch", "dfk_soffsets_write",
     "dfk_sclosures_build", "dfk_sclosures_build_arrays", "dfk_sclosures_stats", "dfk_sclosures_fetch", "dfk_sclosures_write", "dfk_allclosures_write",
+    "dfk_patch_build", "dfk_patch_build_arrays", "dfk_patch_stats", "dfk_patch_fetch", "dfk_patch_write",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -105,6 +106,11 @@ SCLOSURES = ["pairs", "yields", "closable", "none", "over", "closures", "columns
              "us", "us_copy", "us_decode", "us_cons", "us_rows", "sum", "xor"]
 SCLOSURES_FILE = "a.stack.closures"
 ALLCLOSURES_FILE = "a.closures.fastb"
+# dfk_patch_stats' words (include/dfk.h, DFK_PATCH_*)
+PATCH_WORDS = 40
+PATCH = ["edges", "canonical", "vertices", "crossings", "closures", "short", "positions", "found", "new", "new_unique", "bits_added", "kmers3", "canonical3", "vertices3", "edges3", "single3",
+         "cycle_kmers", "path1", "path2", "path3", "to3", "left3", "batches", "us", "us_entries", "us_index", "us_closures", "us_sort", "us_graph", "us_number", "us_paths", "us_copy", "sum", "xor"]
+PATCH_FILES = ("a.patch.k", "a.patch.hbv", "a.patch.hbx", "a.patch.to_left", "a.patch.to_right", "a.patch.inv", "a.patch.fastb", "a.patch.kmers", "a.patch.to3")
 # dfk_adj_outcome's codes (include/dfk.h, DFK_ADJ_*)
 ADJ_OUTCOMES = ["not applicable", "used", "discarded: guess too low", "discarded: list problem", "no block", "dropped for an allocation",
                 "switched off"]
@@ -879,6 +885,46 @@ class Dfk:
         out = (C.c_uint64 * 4)()
         _check(lib().dfk_allclosures_write(self._ctx, None if directory is None else str(directory).encode(), out))
         return dict(closures=int(out[0]), bases=int(out[1]), stackster=int(out[2]), closegap2=int(out[3]))
+
+    def patch_build(self, kmers_per_batch=0):
+        """dfk_patch_build: the patched graph hb3 and the old edges' paths to3 / left3 from the context's graph and both closers' closures,
+        after closures_build and sclosures_build over the same pairs.  Returns patch_stats()."""
+        _check(lib().dfk_patch_build(self._ctx, C.c_uint64(kmers_per_batch)))
+        return self.patch_stats()
+
+    def patch_build_arrays(self, inv, to_left, to_right, n_vertices, packed, edge_off, edge_len, closure_starts, closure_bases, kmers_per_batch=0):
+        """dfk_patch_build_arrays: the same stage on arrays.  The graph: inv, to_left, to_right int32[n_edges], its edges' bases packed four to
+        the byte, edge e at byte edge_off[e] with edge_len[e] bases; the closures: starts uint64[n + 1] into closure_bases uint8[] (0-3).
+        Returns patch_stats()."""
+        room = lambda a, t: np.ascontiguousarray(a if len(a) else np.zeros(1, t), t)     # (an empty array still has an address)
+        n = len(inv)
+        inv, to_left, to_right = room(inv, np.int32), room(to_left, np.int32), room(to_right, np.int32)
+        packed, edge_off, edge_len = room(packed, np.uint8), room(edge_off, np.uint64), room(edge_len, np.uint32)
+        closure_starts = np.ascontiguousarray(closure_starts, np.uint64); closure_bases = room(closure_bases, np.uint8)
+        _check(lib().dfk_patch_build_arrays(self._ctx, C.c_uint64(n), C.c_uint64(n_vertices), _p(inv), _p(to_left), _p(to_right), _p(packed), _p(edge_off), _p(edge_len),
+                                            C.c_uint64(len(closure_starts) - 1), _p(closure_starts), _p(closure_bases), C.c_uint64(kmers_per_batch)))
+        return self.patch_stats()
+
+    def patch_stats(self):
+        """dfk_patch_stats: {counter: value} -- the old graph, the closures and their K-mers (found, new, new after de-duplication, context
+        bits added), hb3, the old edges' paths by length, to3 entries, nonzero left3, batches, times, digest."""
+        out = (C.c_uint64 * PATCH_WORDS)()
+        _check(lib().dfk_patch_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(PATCH)}
+
+    def patch_fetch(self):
+        """dfk_patch_fetch: dict(to3_first uint64[E + 1], to3 int32[], left3 int32[E], kmers, inv, to_left, to_right int32[E3] of hb3)."""
+        ne, nt, n3 = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().dfk_patch_fetch(self._ctx, C.byref(ne), C.byref(nt), C.byref(n3), None, None, None, None, None, None, None))
+        first = np.zeros(ne.value + 1, np.uint64)
+        to3, left3 = np.zeros(max(1, nt.value), np.int32), np.zeros(max(1, ne.value), np.int32)
+        g = [np.zeros(max(1, n3.value), np.int32) for _ in range(4)]
+        _check(lib().dfk_patch_fetch(self._ctx, None, None, None, _p(first), _p(to3), _p(left3), _p(g[0]), _p(g[1]), _p(g[2]), _p(g[3])))
+        return dict(to3_first=first, to3=to3[: nt.value], left3=left3[: ne.value], kmers=g[0][: n3.value], inv=g[1][: n3.value], to_left=g[2][: n3.value], to_right=g[3][: n3.value])
+
+    def patch_write(self, directory):
+        """dfk_patch_write: a.patch.{k,hbv,hbx,to_left,to_right,inv,fastb,kmers} and a.patch.to3 into `directory` (which must exist)."""
+        _check(lib().dfk_patch_write(self._ctx, None if directory is None else str(directory).encode()))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
