@@ -4,14 +4,16 @@ tests/patch_oracle.py: the nine files a.patch.* byte for byte, to3_first, to3, l
 tests/patch_cases.py with kmers_per_batch 1, 37 and 0; the no-closure case on two fixtures' own files (K = 40 and 48) against the files the
 reference wrote; each refusal with the earlier result still served and the next good call behind it; the chain after a real dfk_count ...
 dfk_sclosures_build on two fixtures, with dfk_paths_build afterwards giving the paths it gave before; `DF ... CLOSURES=True SCLOSURES=True
-PATCH=True` on frag with its 657 closures against the oracle's files, its refusals, and DF without the switch.  Everything is exact."""
+PATCH=True` on frag with its 657 closures against the oracle's files, its refusals, and DF without the switch.  Everything is exact.
+Whatever the device returned or wrote is also held to tests/patch_seeded.py's check_invariants, which asks no oracle: every old edge read
+back off hb3 along to3 from left3, and hb3 holding together."""
 import os
 
 import numpy as np
 import pytest
 
 from oracle import graph_oracle as go
-from tests import patch_cases, patch_oracle as po
+from tests import patch_cases, patch_oracle as po, patch_seeded
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +40,15 @@ def arrays(g, closures):
             np.asarray([len(s) for s in g["edges"]], np.uint32), starts, np.frombuffer(b"".join(bytes(c) for c in closures), np.uint8))
 
 
-def check(d, st, want, tmp_path, sub, what):
+def written_edges(directory):
+    """hb3's edges by id as a.patch.fastb in `directory` holds them"""
+    from superplus_amd import feudal
+    packed, off, ln = feudal.read_fastb(os.path.join(directory, "a.patch.fastb"))
+    return po.unpack(packed.tobytes(), np.asarray(off, np.int64) - int(off[0]), ln) if len(ln) else []
+
+
+def check(d, st, want, tmp_path, sub, what, g, closures):
+    """the device's result against the oracle's `want`, then by itself against the old graph `g` and the closures"""
     got = d.patch_fetch()
     first = np.concatenate([[0], np.cumsum([len(p) for p in want["to3"]])])
     assert [int(x) for x in got["to3_first"]] == [int(x) for x in first], f"{what}: to3_first"
@@ -55,6 +65,9 @@ def check(d, st, want, tmp_path, sub, what):
     assert d.stats()["hbm_held"] == held and sorted(os.listdir(out)) == sorted(want["files"])
     for f in want["files"]:
         assert open(os.path.join(out, f), "rb").read() == want["files"][f], f"{what}: {f}"
+    first = [int(x) for x in got["to3_first"]]
+    patch_seeded.check_invariants(g, closures, written_edges(out), got["inv"], got["to_left"], got["to_right"], [[int(x) for x in got["to3"][a:b]] for a, b in zip(first, first[1:])],
+                                  got["left3"], got["kmers"], what)
 
 
 # ---- 1. the hand-made and seeded cases
@@ -83,7 +96,7 @@ def test_arrays_match_the_oracle(ctx, cases, tmp_path, name):
         held = d.stats()["hbm_held"]
         st = d.patch_build_arrays(*arrays(g, closures), per)
         assert d.stats()["hbm_held"] == held
-        check(d, st, want, tmp_path, f"per{per}", f"{name} kmers_per_batch={per}")
+        check(d, st, want, tmp_path, f"per{per}", f"{name} kmers_per_batch={per}", g, closures)
         assert st["batches"] == ((n + per - 1) // per if per else (1 if n else 0))
     assert st["cycle_kmers"] == (160 if name == "cycle" else 0)
     if name == "join": assert st["batches"] == 1 and n == 75                    # (37: three batches, asserted above)
@@ -94,7 +107,7 @@ def test_all_cases_are_run(cases):
 
 
 # ---- 2. no closures: the fixture's own files come back
-@pytest.mark.parametrize("case,K", [("graph_special_k48", 48), ("graph_k40_nobc", 40)])
+@pytest.mark.parametrize("case,K", [("graph_special_k48", 48), ("graph_k40_nobc", 40), ("graph_k60_nobc", 60), ("graph_zoo_k40", 40), ("graph_zoo_k48", 48), ("graph_zoo_k60", 60)])
 def test_without_closures_the_fixture_comes_back(golden_dir, tmp_path, case, K):
     from superplus_amd.dfk import Dfk
     g = po.fixture_graph(golden_dir, case, K)
@@ -129,7 +142,7 @@ def test_refusals(ctx, cases, tmp_path):
         with pytest.raises(DfkError) as e:
             d.patch_build_arrays(*arrays(bad, closures))
         assert e.value.code == -1 and d.stats()["hbm_held"] == held, name      # DFK_E_ARG
-        check(d, d.patch_stats(), want, tmp_path, "after_" + name, "after the refusal " + name)
+        check(d, d.patch_stats(), want, tmp_path, "after_" + name, "after the refusal " + name, g, closures)
     a = list(arrays(g, closures))
     fell = a[7].copy(); fell[1] = fell[2] + 1
     late = a[7].copy(); late[0] = 1
@@ -139,12 +152,12 @@ def test_refusals(ctx, cases, tmp_path):
         with pytest.raises(DfkError) as e:
             d.patch_build_arrays(*bad_args)
         assert e.value.code == -1 and d.stats()["hbm_held"] == held, what
-        check(d, d.patch_stats(), want, tmp_path, "after_closures", "after the refusal: " + what)
+        check(d, d.patch_stats(), want, tmp_path, "after_closures", "after the refusal: " + what, g, closures)
     with pytest.raises(DfkError) as e:                                          # a context without a graph of its own has nothing to patch
         d.patch_build()
     assert e.value.code == -6
     g2, cl2, want2 = cases["join"]
-    check(d, d.patch_build_arrays(*arrays(g2, cl2), 37), want2, tmp_path, "next", "the next good call")
+    check(d, d.patch_build_arrays(*arrays(g2, cl2), 37), want2, tmp_path, "next", "the next good call", g2, cl2)
 
 
 # ---- 4. the chain after a real count
@@ -155,7 +168,8 @@ def test_chain_on_the_fixtures(golden_dir, tmp_path, case, K, which):
     from tests.test_gpu_hops import ARRAYS
     from tests.test_gpu_sclosures import READS, interleaved
     closures = [bytes(np.asarray(c, np.uint8)) for c in interleaved(golden_dir, case, K, which)[0]]
-    want = po.run(po.fixture_graph(golden_dir, case, K), closures)
+    g = po.fixture_graph(golden_dir, case, K)
+    want = po.run(g, closures)
     d, rs, i = partnered(golden_dir, tmp_path, case, K, which)
     reads = tuple(rs[k] for k in READS)
     before = d.paths()
@@ -170,8 +184,8 @@ def test_chain_on_the_fixtures(golden_dir, tmp_path, case, K, which):
     held = d.stats()["hbm_held"]
     st = d.patch_build()
     assert d.stats()["hbm_held"] == held and st["closures"] == len(closures)
-    check(d, st, want, tmp_path, "chain", case)
-    check(d, d.patch_build(37), want, tmp_path, "chain37", case + " kmers_per_batch=37")
+    check(d, st, want, tmp_path, "chain", case, g, closures)
+    check(d, d.patch_build(37), want, tmp_path, "chain37", case + " kmers_per_batch=37", g, closures)
     # the context's own graph and pathing state are untouched: pathing the reads again gives what it gave
     d.paths_build(*(rs[k] for k in ARRAYS))
     after = d.paths()
@@ -192,7 +206,8 @@ def test_df_writes_the_patched_graph(tmp_path, golden_dir):
     case, K, which = FIXTURES[0]
     seqs, n_s, n_g = interleaved(golden_dir, case, K, which)
     assert n_s + n_g == 657
-    want = po.run(po.fixture_graph(golden_dir, case, K), [bytes(np.asarray(c, np.uint8)) for c in seqs])
+    g, closures = po.fixture_graph(golden_dir, case, K), [bytes(np.asarray(c, np.uint8)) for c in seqs]
+    want = po.run(g, closures)
     r = run_df(tmp_path, golden_dir, which, *df_args(), "PATCH=True")
     assert r.returncode == 0, r.stdout + r.stderr
     w = f"{tmp_path}/GapToy/1/a.48"
@@ -208,6 +223,15 @@ def test_df_writes_the_patched_graph(tmp_path, golden_dir):
                      '"edges3": %d, "to3": %d, "left3": %d, "a.patch.to3": "%016x%016x", "batches": 1}'
                      % (*(c[k] for k in ("edges", "closures", "positions", "found", "new", "new_unique", "bits_added", "kmers3", "canonical3", "vertices3", "edges3", "to3", "left3")), *want["digest"])], lines
     assert r.stdout.index("found 657 closures") < r.stdout.index("DF_PATCH ")
+    # what DF wrote, by itself: the tables read back from its files
+    from tests.hops_oracle import read_ints
+    f = open(f"{w}/a.patch.to3", "rb").read()
+    E, n = (int(x) for x in np.frombuffer(f, "<u8", 2, 8))
+    first = [int(x) for x in np.frombuffer(f, "<u8", E + 1, 24)]
+    to3, left3 = np.frombuffer(f, "<i4", n, 24 + 8 * (E + 1)), np.frombuffer(f, "<i4", E, 24 + 8 * (E + 1) + 4 * n)
+    assert f[:8] == po.MAGIC and E == len(g["edges"]) and len(f) == 24 + 8 * (E + 1) + 4 * n + 4 * E
+    patch_seeded.check_invariants(g, closures, written_edges(w), read_ints(f"{w}/a.patch.inv"), read_ints(f"{w}/a.patch.to_left"), read_ints(f"{w}/a.patch.to_right"),
+                                  [[int(x) for x in to3[a:b]] for a, b in zip(first, first[1:])], left3, read_ints(f"{w}/a.patch.kmers"), "DF on frag")
 
 
 def test_df_refuses_patch_without_both_closers_or_sharded(tmp_path, golden_dir):
