@@ -1034,6 +1034,56 @@ int dfk_patch_fetch(dfk_ctx* ctx, uint64_t* n_edges, uint64_t* n_to3, uint64_t* 
                     int32_t* to_right3);
 int dfk_patch_write(dfk_ctx* ctx, const char* dir);
 
+/* ---- the end of the patching stage: the read paths moved onto the patched graph (TranslatePaths, paths/long/large/GapToyTools4.cc:163-196,
+ * and the Validate behind it; 10X/runstages/RunStages.cc:364-371) ----
+ * Every placed read becomes a path of ONE hb3 edge with a new offset, or loses its path (and keeps its old offset).  The rule, the
+ * bound that lets the device decide every path the pather can make, the plan and the layout: csrc/dfk_translate.h.  The result is a
+ * second list of path batches in the arena, batch for batch beside the context's paths, which stay as they are; it is released by
+ * dfk_translate_drop, by the next dfk_translate_build*, and with the paths.  A refused call changes nothing and the earlier result is
+ * still served.  Not for the ranks of a sharded run.
+ *   dfk_translate_build         DFK_E_STATE unless the context holds built paths and a dfk_patch_build result (one made by
+ *                               dfk_patch_build_arrays does not count: its graph need not be the paths')
+ *   dfk_translate_build_arrays  the same on host arrays and with nothing on the context but its K: to3_first ([n_edges + 1], from 0, not
+ *                               falling; a list may be empty), to3 (ids in [0, n_edges3)), left3 ([n_edges]), kmers3 ([n_edges3], >= 1);
+ *                               the paths as dfk_hops_build_arrays takes them (first [n_reads + 1], edges, ids in [0, n_edges)) with
+ *                               offsets ([n_reads]), cut into batches of reads_per_batch (0 = one).  dir: NULL, or where a.patch.paths is
+ *                               written too.  DFK_E_ARG for a null argument, a table that breaks the above, |offset| or |left3| of 2^30 or
+ *                               more, n_reads >= 2^31 and a batch of 2^32 bytes.
+ *   dfk_translate_stats         out[DFK_TRANSLATE_WORDS]: the counters below
+ *   dfk_translate_fetch         offsets[n_reads], first_edge[n_reads + 1], edges (edges_cap >= DFK_TRANSLATE_PLACED), as dfk_paths_fetch
+ *   dfk_translate_write         dir/a.patch.paths: the feudal ReadPathVec that ReadPathVec::WriteAll would write of `paths` on return from
+ *                               StagePatch, by the code that writes a.paths
+ *   dfk_translate_drop          the result's blocks go back to the arena (no result: nothing happens) */
+#define DFK_TRANSLATE_WORDS 32
+#define DFK_TRANSLATE_READS 0           /* reads, */
+#define DFK_TRANSLATE_PLACED_BEFORE 1   /* of them with a path before */
+#define DFK_TRANSLATE_STEP2 2           /* taken by the first hb3 edge of to3[path[0]] (start < its Bases), */
+#define DFK_TRANSLATE_WALK 3            /* by the walk over the ids, */
+#define DFK_TRANSLATE_CLEARED_EMPTY 4   /* cleared: to3[path[0]] is empty, */
+#define DFK_TRANSLATE_CLEARED_RANOFF 5  /* cleared: the walk ran off the end of p */
+#define DFK_TRANSLATE_HOST 6            /* decided on the host: the walk ran off to3[path[0]] (0 on a context's own paths) */
+#define DFK_TRANSLATE_INVALID 7         /* edge ids Validate would refuse (must be 0) */
+#define DFK_TRANSLATE_EDGE_CHANGED 8    /* reads placed before whose edge is no longer path[0] (a cleared read's is not), */
+#define DFK_TRANSLATE_OFFSET_CHANGED 9  /* whose offset changed */
+#define DFK_TRANSLATE_BATCHES 10        /* batches */
+#define DFK_TRANSLATE_PLACED 11         /* reads with a path now = the edges of the result */
+#define DFK_TRANSLATE_VAR_BYTES 12      /* bytes of the result's variable data */
+#define DFK_TRANSLATE_US 13             /* microseconds: the build call from its first statement, */
+#define DFK_TRANSLATE_US_DECIDE 14      /* k_tp_decide, */
+#define DFK_TRANSLATE_US_HOST 15        /* the host route (copies, the literal rule, k_tp_override), */
+#define DFK_TRANSLATE_US_SCAN 16        /* the scans, */
+#define DFK_TRANSLATE_US_EMIT 17        /* k_tp_emit, */
+#define DFK_TRANSLATE_US_COPY 18        /* tables checked and sent, scratch, counters back */
+#define DFK_TRANSLATE_SUM 19            /* the content digest as DFK_CK_PATHS_SUM/XOR form it: over reads r of h(r, offset, lastSkip, edge) */
+#define DFK_TRANSLATE_XOR 20
+int dfk_translate_build(dfk_ctx* ctx);
+int dfk_translate_build_arrays(dfk_ctx* ctx, uint64_t n_edges, const uint64_t* to3_first, const int32_t* to3, const int32_t* left3, uint64_t n_edges3, const int32_t* kmers3,
+                               uint64_t n_reads, const uint64_t* first /* [n_reads + 1] */, const int32_t* edges, const int32_t* offsets, uint64_t reads_per_batch, const char* dir);
+int dfk_translate_stats(dfk_ctx* ctx, uint64_t* out /* [DFK_TRANSLATE_WORDS] */);
+int dfk_translate_fetch(dfk_ctx* ctx, int32_t* offsets, uint64_t* first_edge, int32_t* edges, uint64_t edges_cap);
+int dfk_translate_write(dfk_ctx* ctx, const char* dir);
+int dfk_translate_drop(dfk_ctx* ctx);
+
 /* ---- rows f-1 / f-2 / f-4 checked where no oracle runs (tests/test_gpu_fullsize_graph.py; DF prints the digests) ----
  * Replaces nothing in the reference (its nearest thing is hbv.CheckSum() / Validate(hbv, paths), 10X/DF.cc:597-598).
  * dfk_paths_digest  fills out[DFK_CHECK_WORDS] with digests that depend on the CONTENT of a.paths, a.paths.inv, a.countsb and

@@ -552,7 +552,7 @@ int main(int argc, char** argv)
         {"K", "48"}, {"MIN_FREQ", "3"}, {"MIN_BC", "2"}, {"MIN_QUAL", "7"}, {"ROOT", "/mnt/assembly"}, {"INSTANCE", "1"},
         {"OUT_DIR", ""}, {"LR", ""}, {"LR_SELECT_FRAC", "1.0"}, {"EXIT_LOAD", "False"}, {"DEVICE", "0"}, {"MAX_MEM_GB", "0"},
         {"HBM_GB", "0"}, {"NUM_THREADS", "-1"}, {"MINIMIZER", "0"}, {"KVEC", "Auto"}, {"KVEC_SORTED", "False"}, {"GRAPH", "True"}, {"PATHS", "True"}, {"LINK_READS", "False"}, {"NUM_GPUS", "1"}, {"PATHS_RESERVE", "20"}, {"BADS", "False"},
-        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}, {"WALKS", "False"}, {"SCONS", "False"}, {"SOFFSETS", "False"}, {"SCLOSURES", "False"}, {"PATCH", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
+        {"HOPS", "False"}, {"ONE_GOOD", "True"}, {"SUBSET", "False"}, {"CLOSER", "False"}, {"PARTNERS", "False"}, {"CONS", "False"}, {"OFFSETS", "False"}, {"CLOSURES", "False"}, {"WALKS", "False"}, {"SCONS", "False"}, {"SOFFSETS", "False"}, {"SCLOSURES", "False"}, {"PATCH", "False"}, {"TRANSLATE", "False"}};                                                     // ONE_GOOD: the reference's name and default (10X/DF.cc:134)
     std::string command = "DF";
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i]; command += " " + s;
@@ -624,6 +624,11 @@ int main(int argc, char** argv)
     // the combined list of both closers' closures; it runs where a.closures.fastb is written and, like HOPS=True, which the closers need, on one GPU only
     if (truthy(a["PATCH"]) && !(want_closures && want_sclosures)) give_up("PATCH=True needs CLOSURES=True and SCLOSURES=True: the patched graph is built from both closers' closures");
     const bool want_patch = truthy(a["PATCH"]);
+
+    // TRANSLATE=True (the read paths moved onto the patched graph, TranslatePaths and Validate, RunStages.cc:364-371; a.<K>/a.patch.paths) works from the paths
+    // on the device and PATCH=True's to3 / left3; it runs behind it and, like HOPS=True, which the closers need, on one GPU only
+    if (truthy(a["TRANSLATE"]) && !want_patch) give_up("TRANSLATE=True needs PATCH=True: the paths are moved with the to3 / left3 the patched graph's build leaves");
+    const bool want_translate = truthy(a["TRANSLATE"]);
 
     std::string work_dir = a["ROOT"] + "/GapToy/" + a["INSTANCE"];                                  // DF.cc:221-222
     if (!a["OUT_DIR"].empty()) work_dir = a["OUT_DIR"];
@@ -1195,6 +1200,17 @@ int main(int argc, char** argv)
                                                        (unsigned long long)pt[DFK_PATCH_NEW], (unsigned long long)pt[DFK_PATCH_NEW_UNIQUE], (unsigned long long)pt[DFK_PATCH_BITS_ADDED], (unsigned long long)pt[DFK_PATCH_KMERS3],
                                                        (unsigned long long)pt[DFK_PATCH_CANONICAL3], (unsigned long long)pt[DFK_PATCH_VERTICES3], (unsigned long long)pt[DFK_PATCH_EDGES3], (unsigned long long)pt[DFK_PATCH_TO3],
                                                        (unsigned long long)pt[DFK_PATCH_LEFT3], (unsigned long long)pt[DFK_PATCH_SUM], (unsigned long long)pt[DFK_PATCH_XOR], (unsigned long long)pt[DFK_PATCH_BATCHES]);
+                                                if (want_translate) {           // the paths onto hb3 (RunStages.cc:364-371): a.<K>/a.patch.paths, after a.patch.*
+                                                    uint64_t tr[DFK_TRANSLATE_WORDS] = {};
+                                                    if (dfk_translate_build(ctx) || dfk_translate_write(ctx, dir.c_str()) || dfk_translate_stats(ctx, tr)) throw std::runtime_error(dfk_last_error());
+                                                    printf("DF_TRANSLATE {\"reads\": %llu, \"placed_before\": %llu, \"step2\": %llu, \"walk\": %llu, \"cleared_empty\": %llu, \"cleared_ranoff\": %llu, \"host\": %llu, "
+                                                           "\"invalid\": %llu, \"edge_changed\": %llu, \"offset_changed\": %llu, \"placed\": %llu, \"a.patch.paths\": \"%016llx%016llx\", \"batches\": %llu}\n",
+                                                           (unsigned long long)tr[DFK_TRANSLATE_READS], (unsigned long long)tr[DFK_TRANSLATE_PLACED_BEFORE], (unsigned long long)tr[DFK_TRANSLATE_STEP2],
+                                                           (unsigned long long)tr[DFK_TRANSLATE_WALK], (unsigned long long)tr[DFK_TRANSLATE_CLEARED_EMPTY], (unsigned long long)tr[DFK_TRANSLATE_CLEARED_RANOFF],
+                                                           (unsigned long long)tr[DFK_TRANSLATE_HOST], (unsigned long long)tr[DFK_TRANSLATE_INVALID], (unsigned long long)tr[DFK_TRANSLATE_EDGE_CHANGED],
+                                                           (unsigned long long)tr[DFK_TRANSLATE_OFFSET_CHANGED], (unsigned long long)tr[DFK_TRANSLATE_PLACED], (unsigned long long)tr[DFK_TRANSLATE_SUM],
+                                                           (unsigned long long)tr[DFK_TRANSLATE_XOR], (unsigned long long)tr[DFK_TRANSLATE_BATCHES]);
+                                                }
                                             }
                                         }
                                     }

@@ -2289,5 +2289,6 @@ int dfk_adj_outcome(dfk_ctx* c, uint32_t* outcome, uint64_t* slots)
 #include "dfk_soffsets.inc"
 #include "dfk_sclosures.inc"
 #include "dfk_patch.inc"
+#include "dfk_translate.inc"
 #include "dfk_paths_shard.inc"
 #include "dfk_pbf.inc"

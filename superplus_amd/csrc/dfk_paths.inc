@@ -28,7 +28,7 @@ struct PathState {
     dfk_ctx* c = nullptr;
     std::string sink_path;                             // asked for by dfk_paths_sink, for the next build
     PathSink* sink = nullptr;                          // the one at work (or done, waiting for dfk_paths_write)
-    ~PathState() { sink_abort(this); if (shard && shard_free) shard_free(shard); if (sub && sub_free) sub_free(sub); if (closer && closer_free) closer_free(closer); if (partners && partners_free) partners_free(partners); if (cons && cons_free) cons_free(cons); }
+    ~PathState() { sink_abort(this); if (shard && shard_free) shard_free(shard); if (sub && sub_free) sub_free(sub); if (closer && closer_free) closer_free(closer); if (partners && partners_free) partners_free(partners); if (cons && cons_free) cons_free(cons); if (translate && translate_free) translate_free(nullptr, translate); }
     DevBuf xlat, he_ce, he_left, he_right, from_start, from_vtx, from_edge, to_start, to_vtx, to_edge;
     bool tables = false;
     std::vector<PathBatch> batches;
@@ -45,6 +45,8 @@ struct PathState {
     void (*partners_free)(struct PartnersResult*) = nullptr;
     struct ConsResult* cons = nullptr;                // the stacks' consensus per pair and side (dfk_cons_build, dfk_cons.inc): host memory
     void (*cons_free)(struct ConsResult*) = nullptr;
+    struct TranslateResult* translate = nullptr;      // the paths on the patched graph (dfk_translate_build*, dfk_translate.inc): a second list of batches in the arena
+    void (*translate_free)(dfk_ctx*, struct TranslateResult*) = nullptr;   // (a null context: the blocks have gone with the arena)
     uint64_t ck[DFK_CHECK_WORDS] = {};                // dfk_paths_digest: what the steps so far have left (ck[DFK_CK_VALID]: which)
     int64_t read_id0 = 0;                             // a rank of a sharded run: the whole set's number of its first read (dfk_paths_shard.inc)
     void* shard = nullptr; void (*shard_free)(void*) = nullptr;
@@ -68,6 +70,8 @@ void paths_drop_results(dfk_ctx* c, PathState* P)
     P->partners = nullptr;
     if (P->cons && P->cons_free) P->cons_free(P->cons);
     P->cons = nullptr;
+    if (P->translate && P->translate_free) P->translate_free(c, P->translate);
+    P->translate = nullptr;
     for (uint64_t& w : P->ck) w = 0;
 }
 
@@ -435,6 +439,30 @@ int write_pieces(dfk_ctx* c, int fd, const std::vector<FilePiece>& pieces, const
             return flush(l, t, k ^ 1);
         },
         [&](unsigned t, XferLane& l) -> int { int r = flush(l, t, 0); return r ? r : flush(l, t, 1); });
+}
+
+// A list of batches as a feudal file of ReadPath into the open `fd`, which is closed: the control block, the size, the last offset, then
+// the batches' data as it is (`streamed`: it is in the file already) and their elements' absolute file offsets -- the 32-bit ones kept
+// per read, widened in the transfer lanes.  Nothing is allocated on the device.  dfk_paths_write's a.paths and dfk_translate_write's
+// a.patch.paths (dfk_translate.inc).
+int path_batches_to_file(dfk_ctx* c, int fd, const char* path, const FeudalLayout& lay, uint64_t n, const std::vector<PathBatch>& batches, bool streamed)
+{
+    const uint64_t var_tab = lay.var_tab;
+    int rc = pwrite(fd, &lay.head, 24, 0) == 24 ? 0 : fail(DFK_E_ARG, "short write to %s", path);
+    if (!rc && ftruncate(fd, (off_t)lay.file_size) != 0) rc = fail(DFK_E_ARG, "cannot size %s", path);
+    const uint64_t last = var_tab;                                            // the (n+1)-th offset: the end of the variable data
+    if (!rc && pwrite(fd, &last, 8, (off_t)(var_tab + 8 * n)) != 8) rc = fail(DFK_E_ARG, "short write to %s", path);
+    if (!rc) {
+        std::vector<FilePiece> pieces;
+        for (const PathBatch& b : batches) {
+            if (!streamed) append_pieces(pieces, (const char*)b.var.p, b.var_bytes, b.file_base, XFER_CHUNK);
+            append_wide_pieces(pieces, (const char*)b.elem_off.p, b.n * 4, var_tab + 8 * b.r0, b.file_base, XFER_CHUNK);
+        }
+        rc = write_pieces(c, fd, pieces);
+        if (rc) rc = fail(DFK_E_ARG, "short write to %s", path);
+    }
+    if (close(fd) != 0 && !rc) rc = fail(DFK_E_ARG, "short write to %s", path);
+    return rc;
 }
 
 // ---- dfk_paths_sink (see PathSink)
@@ -1061,7 +1089,7 @@ int dfk_paths_write(dfk_ctx* c, const char* path)
     // n+1 absolute offsets | no fixed data (ReadPath keeps none outside the variable part)
     const uint64_t n = P->n_reads;
     const FeudalLayout lay = feudal_layout(n, 24, 4, P->var_total);
-    const uint64_t var_tab = lay.var_tab;
+    // This call only reads the context (see dfk.h) and may run on a thread of its own beside the calls that follow it.
     // (with dfk_paths_sink on this path the variable data is in the file already, or on its way: wait for it, add the rest)
     const bool streamed = P->sink && P->sink->path == path;
     if (P->sink && !streamed) return fail(DFK_E_STATE, "the paths are being written to %s (dfk_paths_sink): write that file first", P->sink->path.c_str());
@@ -1069,24 +1097,7 @@ int dfk_paths_write(dfk_ctx* c, const char* path)
     if (streamed) { rc = sink_finish(P, &fd); if (rc) return rc; }
     else fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
     if (fd < 0) return fail(DFK_E_ARG, "cannot open %s", path);
-    rc = pwrite(fd, &lay.head, 24, 0) == 24 ? 0 : fail(DFK_E_ARG, "short write to %s", path);
-    if (!rc && ftruncate(fd, (off_t)lay.file_size) != 0) rc = fail(DFK_E_ARG, "cannot size %s", path);
-    const uint64_t last = var_tab;                                            // the (n+1)-th offset: the end of the variable data
-    if (!rc && pwrite(fd, &last, 8, (off_t)(var_tab + 8 * n)) != 8) rc = fail(DFK_E_ARG, "short write to %s", path);
-    // The batches' data as it is; their elements' absolute file offsets are the 32-bit ones kept per read, widened in the
-    // transfer lanes.  Nothing is allocated on the device: this call only reads the context (see dfk.h) and may run on a
-    // thread of its own beside the calls that follow it.
-    if (!rc) {
-        std::vector<FilePiece> pieces;
-        for (const PathBatch& b : P->batches) {
-            if (!streamed) append_pieces(pieces, (const char*)b.var.p, b.var_bytes, b.file_base, XFER_CHUNK);
-            append_wide_pieces(pieces, (const char*)b.elem_off.p, b.n * 4, var_tab + 8 * b.r0, b.file_base, XFER_CHUNK);
-        }
-        rc = write_pieces(c, fd, pieces);
-        if (rc) rc = fail(DFK_E_ARG, "short write to %s", path);
-    }
-    if (close(fd) != 0 && !rc) rc = fail(DFK_E_ARG, "short write to %s", path);
-    return rc;
+    return path_batches_to_file(c, fd, path, lay, n, P->batches, streamed);
     });
 }
 

@@ -43,6 +43,7 @@ EXPORTS = [
     "dfk_soffsets_build", "dfk_soffsets_build_arrays", "dfk_soffsets_stats", "dfk_soffsets_fetch", "dfk_soffsets_write",
     "dfk_sclosures_build", "dfk_sclosures_build_arrays", "dfk_sclosures_stats", "dfk_sclosures_fetch", "dfk_sclosures_write", "dfk_allclosures_write",
     "dfk_patch_build", "dfk_patch_build_arrays", "dfk_patch_stats", "dfk_patch_fetch", "dfk_patch_write",
+    "dfk_translate_build", "dfk_translate_build_arrays", "dfk_translate_stats", "dfk_translate_fetch", "dfk_translate_write", "dfk_translate_drop",
 ]
 
 # dfk_paths_digest's words (include/dfk.h, DFK_CK_*) and dfk_paths_verify's counters
@@ -111,6 +112,11 @@ PATCH_WORDS = 40
 PATCH = ["edges", "canonical", "vertices", "crossings", "closures", "short", "positions", "found", "new", "new_unique", "bits_added", "kmers3", "canonical3", "vertices3", "edges3", "single3",
          "cycle_kmers", "path1", "path2", "path3", "to3", "left3", "batches", "us", "us_entries", "us_index", "us_closures", "us_sort", "us_graph", "us_number", "us_paths", "us_copy", "sum", "xor"]
 PATCH_FILES = ("a.patch.k", "a.patch.hbv", "a.patch.hbx", "a.patch.to_left", "a.patch.to_right", "a.patch.inv", "a.patch.fastb", "a.patch.kmers", "a.patch.to3")
+# dfk_translate_stats' words (include/dfk.h, DFK_TRANSLATE_*)
+TRANSLATE_WORDS = 32
+TRANSLATE = ["reads", "placed_before", "step2", "walk", "cleared_empty", "cleared_ranoff", "host", "invalid", "edge_changed", "offset_changed", "batches", "placed", "var_bytes",
+             "us", "us_decide", "us_host", "us_scan", "us_emit", "us_copy", "sum", "xor"]
+TRANSLATE_FILE = "a.patch.paths"
 # dfk_adj_outcome's codes (include/dfk.h, DFK_ADJ_*)
 ADJ_OUTCOMES = ["not applicable", "used", "discarded: guess too low", "discarded: list problem", "no block", "dropped for an allocation",
                 "switched off"]
@@ -925,6 +931,55 @@ class Dfk:
     def patch_write(self, directory):
         """dfk_patch_write: a.patch.{k,hbv,hbx,to_left,to_right,inv,fastb,kmers} and a.patch.to3 into `directory` (which must exist)."""
         _check(lib().dfk_patch_write(self._ctx, None if directory is None else str(directory).encode()))
+
+    def translate_build(self):
+        """dfk_translate_build: the context's paths moved onto the patched graph dfk_patch_build left (TranslatePaths), as a second list of
+        batches on the device; the context's own paths stay.  Returns translate_stats()."""
+        _check(lib().dfk_translate_build(self._ctx))
+        return self.translate_stats()
+
+    def translate_build_arrays(self, to3_first, to3, left3, kmers3, paths, reads_per_batch=0, directory=None):
+        """dfk_translate_build_arrays: the same on arrays.  to3_first uint64[n_edges + 1], to3 int32[], left3 int32[n_edges], kmers3
+        int32[n_edges3]; paths as [(offset, [edges])...] or the tuple paths() returns, cut into batches of reads_per_batch (0 = one);
+        directory: where a.patch.paths is written too, or None.  Returns translate_stats()."""
+        room = lambda a, t: np.ascontiguousarray(a if len(a) else np.zeros(1, t), t)     # (an empty array still has an address)
+        if isinstance(paths, tuple):
+            offsets, first, edges = paths
+        else:
+            offsets = np.array([o for o, _ in paths], np.int64)
+            first = np.zeros(len(paths) + 1, np.uint64)
+            first[1:] = np.cumsum([len(p) for _, p in paths], dtype=np.uint64)
+            edges = np.array([e for _, p in paths for e in p], np.int64)
+        n, n_edges, n_edges3 = len(offsets), len(left3), len(kmers3)
+        to3_first = np.ascontiguousarray(to3_first, np.uint64); first = np.ascontiguousarray(first, np.uint64)
+        assert len(to3_first) == n_edges + 1 and len(first) == n + 1
+        to3, left3, kmers3, offsets, edges = room(to3, np.int32), room(left3, np.int32), room(kmers3, np.int32), room(offsets, np.int32), room(edges, np.int32)
+        _check(lib().dfk_translate_build_arrays(self._ctx, C.c_uint64(n_edges), _p(to3_first), _p(to3), _p(left3), C.c_uint64(n_edges3), _p(kmers3), C.c_uint64(n), _p(first), _p(edges),
+                                                _p(offsets), C.c_uint64(reads_per_batch), None if directory is None else str(directory).encode()))
+        return self.translate_stats()
+
+    def translate_stats(self):
+        """dfk_translate_stats: {counter: value} -- reads, placed before, taken by the first hb3 edge / by the walk, cleared for an empty to3 /
+        by running off, decided on the host, ids Validate would refuse, edges / offsets changed, batches, placed now, bytes, times, digest."""
+        out = (C.c_uint64 * TRANSLATE_WORDS)()
+        _check(lib().dfk_translate_stats(self._ctx, out))
+        return {k: int(out[i]) for i, k in enumerate(TRANSLATE)}
+
+    def translate_fetch(self):
+        """dfk_translate_fetch -> (offsets i32[n], first_edge u64[n+1], edges i32[...]), as paths()"""
+        st = self.translate_stats()
+        off = np.zeros(max(1, st["reads"]), np.int32); first = np.zeros(st["reads"] + 1, np.uint64)
+        edges = np.zeros(max(1, st["placed"]), np.int32)
+        _check(lib().dfk_translate_fetch(self._ctx, _p(off), _p(first), _p(edges), C.c_uint64(len(edges))))
+        return off[: st["reads"]], first, edges[: st["placed"]]
+
+    def translate_write(self, directory):
+        """dfk_translate_write: a.patch.paths into `directory` (which must exist)."""
+        _check(lib().dfk_translate_write(self._ctx, None if directory is None else str(directory).encode()))
+
+    def translate_drop(self):
+        """dfk_translate_drop: the translated paths' device blocks go back to the arena."""
+        _check(lib().dfk_translate_drop(self._ctx))
 
     def paths_digest(self):
         """dfk_paths_digest: {name: word} -- content digests of a.paths / a.paths.inv / a.countsb / a.dup and the graph's identities."""
